@@ -11,20 +11,26 @@ the K timed steps last at least --min-timed-ms (300 ms) whatever K is, and the l
 spelled out (host_enqueue_us_per_launch, sync_ms).  With N > 1 every rank unwarps its own ring (independent frames,
 no data-path collective): weak scaling.
 
-After the timed region the same run also measures, outside it and reported beside the headline:
+A plain run does only what the headline needs: set up, settle the clocks, warm up, time the K steps, write the outputs of
+the last step when --dump-outputs DIR is given, print the line.  With --full the same run also checks frame 0 of the timed
+launches against the oracle and measures, outside the timed region and reported beside the headline:
   other_configs   (N = 1) config 2 with scipy's exact blend and at order 0, config 3 fused / two-pass /
                   perspective only, config 5, config 4 on one GPU (whole stack when it fits) and one sinogram --
                   each with its per-launch time from HIP events, the kernel that ran and verified_vs_oracle;
   stack_scaling   (every N) config 4 sharded by depth over the ranks: compute only, and compute + the RCCL
                   all-gather that reassembles the (depth, rows, width) block on every rank -- the two curves
-                  north_star asks for fall out of the driver's N = 1, 2, 4, 8 runs without a flag.
+                  north_star asks for fall out of the N = 1, 2, 4, 8 runs with --full;
+and (N = 1) the per-launch distribution, the batched entry points, NumPy in -> NumPy out timings and
+`cpu_baseline` (oracle/unwarp_oracle.c timed on the host cores).
 
-    python bench.py                      # 1 GPU
+    python bench.py --gpus 1 --steps K --warmup W                    # the headline alone
+    python bench.py --gpus 1 --steps K --warmup W --full             # + verification and every other figure
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR # + DIR/<name>.npy of the last timed step
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the
-dominant kernel and `cpu_baseline` (oracle/unwarp_oracle.c timed on the host cores).
+dominant kernel.
 """
 import argparse
 import json
@@ -68,8 +74,14 @@ def parse(argv=None):
                          "profiles/r06a_dispatch_modes.txt, tools/time_dispatch.py")
     ap.add_argument("--blend", default="f64lerp", choices=sorted(BLEND_NAMES))
     ap.add_argument("--order", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip other_configs and stack_scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify it against the oracle and measure every other figure (other_configs, "
+                         "stack_scaling, per-launch distribution, batched entry points, NumPy in -> NumPy out, cpu_baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample of pixel positions of every frame of the ring, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip other_configs and stack_scaling")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPUs this process may use (affinity, cgroup quota)")
     ap.add_argument("--option", action="append", default=[], help="kernel option key=value (dcp_set_option)")
     ap.add_argument("--workload", default="frame", choices=["frame", "stack"],
@@ -84,12 +96,17 @@ def parse(argv=None):
     ap.add_argument("--child-world", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--child-rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--idfile", default=None, help=argparse.SUPPRESS)
+    # internal: set by spawn_ranks -- the torch-free exchange variants run in the launching process after the ranks have exited
+    ap.add_argument("--native-in-launcher", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-spawn", action="store_true",
                     help="--gpus N > 1 without WORLD_SIZE in the environment normally re-launches itself as N ranks; this keeps one process")
     ap.add_argument("--shard", default="depth", choices=["depth", "rows"],
                     help="stack workload: depth = projections split over the ranks (+ all-gather); rows = every rank owns "
                          "output rows of every projection (the whole stack on every rank, no collective)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.dump_outputs and a.workload != "frame":
+        ap.error("--dump-outputs writes the frames of the headline workload (--workload frame)")
+    return a
 
 
 def kernel_sources_digest():
@@ -438,6 +455,24 @@ def download(buf_ptr, shape, dev, offset=0):
     out = np.empty(shape, np.float32)
     F.check(F.lib().dcp_memcpy(out.ctypes.data, buf_ptr + offset, out.nbytes, F.COPY_D2H, dev, None))
     return out
+
+
+DUMP_SEED = 20251016                 # the pixel positions --dump-outputs samples (the same in every run and every build)
+DUMP_MAX_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(dirname, frames, shape, dev):
+    """--dump-outputs: the output frames of the ring as the last timed step left them -- what a caller of dcp_unwarp_image_f32 would
+    receive.  The whole ring is 1.6 GB at the default --batch, so every frame is sampled at the same fixed, seeded pixel positions
+    (2^18 per frame, fewer when the ring is large): DIR/unwarped_frames_sample.npy, float32, (frames, positions)."""
+    H, W = shape
+    per_frame = min(H * W, 1 << 18, DUMP_MAX_BYTES // (4 * len(frames)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, per_frame, replace=False))
+    out = np.empty((len(frames), per_frame), np.float32)
+    for i, fr in enumerate(frames):
+        out[i] = download(fr.ptr, shape, dev).reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "unwarped_frames_sample.npy"), out)
 
 
 def clocks_under_load(step, sync):
@@ -1318,18 +1353,37 @@ def native_exchange_variants(a, world, depth, steps=3, timeout=None):
 
 def spawn_ranks(a, argv):
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment: re-launch as N ranks through torch.distributed.run (one
-    process per GPU, rendezvous on 127.0.0.1) and pass rank 0's JSON line through."""
+    process per GPU, rendezvous on 127.0.0.1) and pass rank 0's JSON line through.  With --full the torch-free exchange variants
+    (native_exchange_variants) run here, after the ranks have exited, and go into that line: their N processes then never share
+    the GPUs with the N ranks of the torch job."""
     import socket
     import subprocess
     s_ = socket.socket()
     s_.bind(("127.0.0.1", 0))
     port = s_.getsockname()[1]
     s_.close()
-    args = [x for x in (sys.argv[1:] if argv is None else list(argv))]
+    args = [x for x in (sys.argv[1:] if argv is None else list(argv))] + ["--native-in-launcher"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + args
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    return subprocess.run(cmd, env=env, cwd=os.getcwd()).returncode
+    r = subprocess.run(cmd, env=env, cwd=os.getcwd(), stdout=subprocess.PIPE, text=True)
+    lines = r.stdout.split("\n")
+    at = [i for i, ln in enumerate(lines) if ln.startswith("{")]
+    if r.returncode == 0 and at:
+        try:
+            j = json.loads(lines[at[-1]])
+            ss = j.get("stack_scaling")
+            if isinstance(ss, dict) and isinstance(ss.get("without_torch"), dict) and ss["without_torch"].get("pending"):
+                try:
+                    ss["without_torch"] = native_exchange_variants(a, a.gpus, a.depth)
+                except Exception as e:      # noqa: BLE001
+                    ss["without_torch"] = {"error": repr(e)}
+                lines[at[-1]] = json.dumps(j)
+        except ValueError:
+            pass
+    sys.stdout.write("\n".join(lines))
+    sys.stdout.flush()
+    return r.returncode
 
 
 def grid_search_centres(a, dev):
@@ -1491,16 +1545,17 @@ def main(argv=None):
         return
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and not a.no_spawn:
         sys.exit(spawn_ranks(a, argv))
+    extras = a.full and not a.no_extras          # a plain run: the headline alone
     # the drop-in caller's number (NumPy in -> NumPy out) is measured FIRST, in child processes, before this process opens the
     # GPU: with a second process holding a context on the device the /opt/rocm runtime's two-directional host path ran at half
     # its speed (3.76 ms against 1.83 ms per 4096^2 frame)
     e2e = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.no_extras and a.workload == "frame":
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and extras and a.workload == "frame":
         try:
             e2e = end_to_end_numpy()
         except Exception as e:      # noqa: BLE001 -- context only
             e2e = {"error": repr(e)}
-    torch_dbg_dir = rccl_debug_env(os.environ, "torch") if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.no_extras else None
+    torch_dbg_dir = rccl_debug_env(os.environ, "torch") if int(os.environ.get("WORLD_SIZE", "1")) > 1 and extras else None
     world, rank, dev_index, dist, backend = init_dist()
     n_gpus = world
     if a.gpus != world and rank == 0:
@@ -1623,15 +1678,17 @@ def main(argv=None):
         for _ in range(cycles):
             ring_pass()
 
-    # the host's own cost of one launch, on a queue that never fills: 64 calls behind a synchronize (outside the timed region)
-    sync()
-    pairs, n_host = list(zip(srcs, dsts)), 64
-    th0 = time.perf_counter()
-    for i in range(n_host):
-        s, d = pairs[i % len(pairs)]
-        L.dcp_unwarp_image_f32(s.ptr, d.ptr, H, W, W, 1, cfg["xcenter"], cfg["ycenter"], fa, nf, a.order, 1, blend, F.MEM_DEVICE, dev, None)
-    host_call_us = (time.perf_counter() - th0) * 1e6 / n_host
-    sync()
+    # the host's own cost of one launch, on a queue that never fills: 64 calls behind a synchronize (outside the timed region; --full)
+    host_call_us = None
+    if a.full:
+        sync()
+        pairs, n_host = list(zip(srcs, dsts)), 64
+        th0 = time.perf_counter()
+        for i in range(n_host):
+            s, d = pairs[i % len(pairs)]
+            L.dcp_unwarp_image_f32(s.ptr, d.ptr, H, W, W, 1, cfg["xcenter"], cfg["ycenter"], fa, nf, a.order, 1, blend, F.MEM_DEVICE, dev, None)
+        host_call_us = (time.perf_counter() - th0) * 1e6 / n_host
+        sync()
 
     for _ in range(a.warmup):
         step()
@@ -1662,9 +1719,11 @@ def main(argv=None):
         wall, dev_ms = float(tt[0]), float(tt[1])
 
     # ---- everything below is outside the timed region
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, dsts, (H, W), dev)
     verified = None
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:                   # frame 0 of the timed launches against the oracle (kernel arithmetic order, the same blend)
             orc = oracle_module(a.cpu_threads)
             ob = {"scipy": orc.BLEND_SCIPY, "f64lerp": orc.BLEND_F64LERP, "f32lerp": orc.BLEND_F32LERP}[a.blend]
@@ -1692,7 +1751,7 @@ def main(argv=None):
             copy_gbps = None
 
     dist_launch = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:          # per-launch distribution of the headline call (outside the timed region): the mean hides a few slow launches
             def one(i):
                 F.check(L.dcp_unwarp_image_f32(srcs[i % a.batch].ptr, dsts[i % a.batch].ptr, H, W, W, 1, cfg["xcenter"], cfg["ycenter"], fa, nf,
@@ -1701,10 +1760,10 @@ def main(argv=None):
         except Exception as e:      # noqa: BLE001 -- context only
             dist_launch = {"error": repr(e)}
 
-    box = clocks_under_load(ring_pass, sync) if (rank == 0 and n_gpus == 1 and not a.no_extras) else None
+    box = clocks_under_load(ring_pass, sync) if (rank == 0 and n_gpus == 1 and extras) else None
 
     batched = None
-    if rank == 0 and n_gpus == 1 and a.order == 1 and not a.no_extras:
+    if rank == 0 and n_gpus == 1 and a.order == 1 and extras:
         # context, not the metric: the frames of the ring share one calibration and lie in one (batch, H, W) array, so the PUBLIC batch
         # entry point (dcp_unwarp_images_f32: one pointer, centre and coefficient vector per frame) recognises them as the projections
         # of a stack and runs stack_wg_kernel -- bit-identical output, the coordinates evaluated once per pixel position instead of
@@ -1734,7 +1793,7 @@ def main(argv=None):
             batched = {"error": repr(e)}
 
     batched_distinct = None
-    if rank == 0 and n_gpus == 1 and not a.no_extras:
+    if rank == 0 and n_gpus == 1 and extras:
         # beside the per-launch headline, not instead of it: the frames of a step through ONE dcp_unwarp_images_f32 call, every
         # frame with its OWN calibration (centre shifted, coefficients rescaled per frame) -- remap_wg_batch_kernel, the frame in
         # blockIdx.z, so that the drain of one frame runs under the ramp of the next
@@ -1744,7 +1803,7 @@ def main(argv=None):
             batched_distinct = {"error": repr(e)}
 
     others = None
-    if rank == 0 and n_gpus == 1 and not a.no_extras:
+    if rank == 0 and n_gpus == 1 and extras:
         try:
             others = other_configs(a, dev, srcs, dsts, img0)
         except Exception as e:      # noqa: BLE001 -- context only
@@ -1763,7 +1822,7 @@ def main(argv=None):
                 others[name] = {"error": repr(e)}
 
     scaling = None
-    if not a.no_extras:
+    if extras:
         try:
             depth = a.depth
             if world == 1:            # the whole stack needs 2 x 53.7 GB; fall back to one 8-GPU shard if that does not fit
@@ -1794,7 +1853,11 @@ def main(argv=None):
         # the exchange without torch (native RCCL through the C ABI; peer copies): child processes of rank 0, the other ranks wait
         # (on a one-GPU test box -- DCP_BENCH_DEVICE set -- only when DCP_RCCL_PATH names the tests' stand-in for librccl: RCCL
         # itself refuses two ranks on one device)
-        if world > 1 and (os.environ.get("DCP_BENCH_DEVICE") is None or os.environ.get("DCP_RCCL_PATH")) and all_ok:
+        if world > 1 and (os.environ.get("DCP_BENCH_DEVICE") is None or os.environ.get("DCP_RCCL_PATH")) and all_ok and a.native_in_launcher:
+            # launched by spawn_ranks: it runs them once every rank has exited (no rank holds a GPU while they are timed)
+            if rank == 0:
+                scaling["without_torch"] = {"pending": "run by the launching process after the ranks have exited"}
+        elif world > 1 and (os.environ.get("DCP_BENCH_DEVICE") is None or os.environ.get("DCP_RCCL_PATH")) and all_ok:
             sync()
             # the other ranks wait for rank 0's children on the HOST (the job's key-value store): an RCCL barrier would park a spinning
             # kernel on every other GPU while the children are being timed on those very GPUs
@@ -1858,7 +1921,7 @@ def main(argv=None):
             # rank 0's host side of the timed region: the launch loop (it blocks while the queue is full, so this tends to the
             # device time on long regions), the final synchronize, and one launch call on a queue that never fills
             "host_enqueue_us_per_launch": round(enqueue_ms * 1e3 / launches, 3), "sync_ms": round(sync_ms, 3),
-            "host_call_us_per_launch_idle_queue": round(host_call_us, 3),
+            "host_call_us_per_launch_idle_queue": None if host_call_us is None else round(host_call_us, 3),
             "launch_us": round(launch_us, 3),
             # which dispatch mode produced `value`: the per-frame entry point, one calibration per call, in every mode
             "dispatch": {"mode": a.dispatch,
@@ -1893,7 +1956,7 @@ def main(argv=None):
                              "frac": round(configs.BYTES_PER_PIXEL * pix_per_launch / (dist_launch["back_to_back_mean_us"] * 1e-6) / 1e9 / configs.HBM_PEAK_GBPS, 4)},
                          "algorithmic_bytes_per_launch": int(configs.BYTES_PER_PIXEL * pix_per_launch),
                          "d2d_copy_same_frames_GBps": copy_gbps, "per_launch_distribution": dist_launch},
-            "verified_vs_oracle": verified,
+            "verified_vs_oracle": verified, "full": a.full,
         }
         # the other BASELINE configurations as top-level scalars too (whatever keeps only part of this line keeps more than one
         # number): cfg3 fused perspective o radial, cfg4 whole stack on one GPU, cfg5 8192^2 9-term, the colour frame
@@ -1924,7 +1987,7 @@ def main(argv=None):
             out["batched_distinct_calibrations"] = batched_distinct
         if e2e is not None:
             out["end_to_end_numpy"] = e2e
-        if n_gpus == 1 and not a.no_cpu_baseline:
+        if n_gpus == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, img0, blend, a.cpu_threads)
         print(json.dumps(out), flush=True)
     if dist is not None:

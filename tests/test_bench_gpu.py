@@ -1,5 +1,6 @@
-"""GPU suite: bench.py itself -- the line the driver records must carry every configuration, each verified against the
-oracle, and the N > 1 path (depth-sharded config 4 + all-gather) must run.  Two ranks share the one GPU of the test box
+"""GPU suite: bench.py itself -- a plain run times the headline alone and can dump what it computed; with --full the line
+must carry every configuration, each verified against the oracle, and the N > 1 path (depth-sharded config 4 + all-gather)
+must run.  Two ranks share the one GPU of the test box
 through the DCP_BENCH_BACKEND=gloo / DCP_BENCH_DEVICE=0 hooks (RCCL refuses two ranks on one device)."""
 import json
 import os
@@ -19,8 +20,41 @@ def _last_json(text):
     return json.loads(lines[-1])
 
 
+def test_plain_run_times_the_headline_alone_and_dumps_the_last_step(hip, orc, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps, the headline fields, none of what --full
+    adds, and DIR/unwarped_frames_sample.npy -- the ring's output frames at fixed, seeded pixel positions -- equal to the oracle's
+    unwarp of the same inputs at those positions."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from discorpy_amd import configs
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "4",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = _last_json(r.stdout)
+    assert j["steps"] == 7 and j["warmup"] == 2 and j["n_gpus"] == 1 and j["full"] is False
+    assert j["unit"] == "Mpixels/s" and j["higher_is_better"] is True and j["dtype"] == "f64" and j["value"] > 0 and j["ms_per_step"] > 0
+    assert abs(j["ms_per_step"] - j["timed_region_ms"] / 7) / j["ms_per_step"] < 1e-3
+    for key in ("other_configs", "stack_scaling", "cpu_baseline", "end_to_end_numpy", "batched_same_calibration", "batched_distinct_calibrations", "box"):
+        assert key not in j, key
+    assert j["verified_vs_oracle"] is None
+    files = sorted(os.listdir(str(out)))
+    assert files == ["unwarped_frames_sample.npy"]
+    got = np.load(str(out / files[0]))
+    assert got.dtype == np.float32 and got.shape == (4, 1 << 18) and got.nbytes <= 64e6
+    cfg = configs.cfg2()
+    H, W = cfg["shape"]
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(H * W, 1 << 18, replace=False))
+    rng = np.random.default_rng(cfg["seed"])
+    for k in range(2):          # the ring's first two frames, regenerated as bench.py makes them
+        img = rng.random((H, W), dtype=np.float32)
+        want = orc.unwarp_image_backward(img, cfg["xcenter"], cfg["ycenter"], cfg["list_fact"], poly=orc.POLY_KERNEL, blend=orc.BLEND_F64LERP)
+        assert np.array_equal(got[k], want.reshape(-1)[idx]), k
+
+
 def test_bench_line_carries_every_config_verified(hip):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "6"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "6", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -59,7 +93,7 @@ def test_bench_line_carries_every_config_verified(hip):
 
 
 def test_the_drivers_command_is_self_consistent_and_repeatable(hip):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's exact command) -- the timed region lasts
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command, with --full) -- the timed region lasts
     >= 0.25 s whatever --steps is, the wall clock agrees with the device events and with launches x per-launch time to 5 %, the host's
     share is spelled out, and two consecutive runs agree (round 4's 14 ms region moved 25 % with a flat kernel)."""
     runs = []
@@ -70,7 +104,7 @@ def test_the_drivers_command_is_self_consistent_and_repeatable(hip):
     for attempt in range(3):
         if attempt == 2 and close_pair():          # (a third run only when the first two disagree: one outlier of the box is tolerated)
             break
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                            capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         j = _last_json(r.stdout)
@@ -99,7 +133,7 @@ def test_bench_two_ranks_share_the_gpu_through_gloo(hip):
     env = dict(os.environ, DCP_BENCH_BACKEND="gloo", DCP_BENCH_DEVICE="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--depth", "16"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--batch", "4", "--depth", "16", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _last_json(r.stdout)
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["verified_vs_oracle"] is True and "cpu_baseline" not in j
@@ -115,7 +149,8 @@ def test_bench_gpus_n_without_torchrun_spawns_its_own_ranks(hip):
     pytest.importorskip("torch")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DCP_BENCH_BACKEND="gloo", DCP_BENCH_DEVICE="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--depth", "16"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--depth", "16",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
@@ -132,14 +167,16 @@ def _fake_rccl():
 
 
 def test_bench_eight_ranks_on_the_one_gpu_populate_every_exchange_variant(hip):
-    """`python bench.py --gpus 8` as the driver will run it on an 8-GPU node, here with the eight ranks sharing the one GPU: gloo
+    """`python bench.py --gpus 8 --full` as it runs on an 8-GPU node, here with the eight ranks sharing the one GPU: gloo
     carries torch's collectives (DCP_BENCH_BACKEND), tests/c/libfake_rccl.so stands in for librccl in the torch-free children
     (DCP_RCCL_PATH).  One JSON line, n_gpus 8, every variant of the config-4 exchange present and checked against the oracle --
-    the first 8-GPU run must not be the first run of this code."""
+    the first 8-GPU run must not be the first run of this code.  The torch-free variants run in the launching process after the
+    eight ranks have exited, so that never more than eight processes of the run hold the GPU at once."""
     pytest.importorskip("torch")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DCP_BENCH_BACKEND="gloo", DCP_BENCH_DEVICE="0", DCP_RCCL_PATH=_fake_rccl(), FAKE_RCCL_SLOT_MB="16")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2", "--depth", "16"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2", "--depth", "16",
+                        "--full"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]

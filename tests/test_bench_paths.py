@@ -116,3 +116,27 @@ def test_bench_argument_defaults_finish_in_minutes():
     import bench
     a = bench.parse([])
     assert (a.gpus, a.workload, a.batch, a.blend, a.order) == (1, "frame", 24, "f64lerp", 1) and a.steps * a.batch <= 5000
+
+
+def test_dump_outputs_samples_every_frame_at_fixed_positions_within_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs: float32, the same seeded positions in every frame and every run, at most 64 MB whatever the ring's size."""
+    import bench
+
+    class Frame:
+        def __init__(self, k):
+            self.ptr = k
+
+    def fake_download(ptr, shape, dev, offset=0):
+        return np.random.default_rng(100 + ptr).random(shape, dtype=np.float32)
+    monkeypatch.setattr(bench, "download", fake_download)
+    for n, shape in ((3, (300, 500)), (2, (4096, 4096)), (80, (1024, 1024))):
+        d1, d2 = tmp_path / ("a%d_%d" % (n, shape[0])), tmp_path / ("b%d_%d" % (n, shape[0]))
+        bench.dump_outputs(str(d1), [Frame(k) for k in range(n)], shape, -1)
+        bench.dump_outputs(str(d2), [Frame(k) for k in range(n)], shape, -1)
+        assert sorted(os.listdir(str(d1))) == ["unwarped_frames_sample.npy"]
+        a, b = np.load(str(d1 / "unwarped_frames_sample.npy")), np.load(str(d2 / "unwarped_frames_sample.npy"))
+        assert a.dtype == np.float32 and a.shape[0] == n and a.nbytes <= 64e6 and np.array_equal(a, b)
+        assert a.shape[1] == min(shape[0] * shape[1], 1 << 18, bench.DUMP_MAX_BYTES // (4 * n))
+        idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(shape[0] * shape[1], a.shape[1], replace=False))
+        for k in (0, n - 1):
+            assert np.array_equal(a[k], fake_download(k, shape, -1).reshape(-1)[idx])

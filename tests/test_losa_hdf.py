@@ -2,48 +2,28 @@
 (load_hdf_file, load_hdf_object, save_hdf_file, open_hdf_stream, load_image, save_image -- reference
 discorpy/losa/loadersaver.py:84-106, 248-355, 413-451, 560-656) and the stack functions fed by them.
 
-h5py is not installed in the build image: tests/helpers/fake_h5py.py stands in for it (sys.modules["h5py"]).  In the build
-container the REFERENCE's own loadersaver is imported on the same stand-in and must return the same arrays / raise the same
-errors; on the GPU box (no /root/reference) that comparison is skipped and the GPU tests run the example_04.py call sequence
--- image in, metadata file, stack from an HDF dataset read band by band, result streamed into an HDF dataset -- against the
-oracle."""
-import importlib
+h5py is not installed in the build image: tests/helpers/fake_h5py.py stands in for it (sys.modules["h5py"]).  Golden G20
+(tools/gen_golden.py) holds what the REFERENCE's own loadersaver returned, raised and wrote on the same stand-in and the same
+files, and the CPU test must match it; the GPU tests run the example_04.py call sequence -- image in, metadata file, stack from
+an HDF dataset read band by band, result streamed into an HDF dataset -- against the oracle."""
+import json
 import os
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import HOST, ROOT, noise, oblend
+from conftest import HOST, ROOT, golden, noise, oblend
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import fake_h5py  # noqa: E402
 
 from discorpy_amd.losa import loadersaver as losa  # noqa: E402
 
-REF = "/root/reference"
-
-
 @pytest.fixture
 def h5(monkeypatch):
     monkeypatch.setitem(sys.modules, "h5py", fake_h5py)
     return fake_h5py
-
-
-@pytest.fixture
-def ref_losa(h5, monkeypatch):
-    """discorpy.losa.loadersaver of the reference, imported on the stand-in (build container only)."""
-    if not os.path.isdir(os.path.join(REF, "discorpy")):
-        pytest.skip("the reference is not on this box")
-    pytest.importorskip("matplotlib")
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
-    monkeypatch.syspath_prepend(REF)
-    for m in [m for m in sys.modules if m == "discorpy" or m.startswith("discorpy.")]:
-        monkeypatch.delitem(sys.modules, m)
-    mod = importlib.import_module("discorpy.losa.loadersaver")
-    yield mod
-    for m in [m for m in sys.modules if m == "discorpy" or m.startswith("discorpy.")]:
-        sys.modules.pop(m, None)
 
 
 def _stack_file(h5, path, dtype=">u2", shape=(9, 14, 11), key="entry/data/data"):
@@ -152,43 +132,59 @@ def test_images_round_trip(tmp_path):
         losa.load_image(str(tmp_path / "junk.png"))
 
 
-def test_same_results_and_errors_as_the_reference_on_the_same_files(ref_losa, h5, tmp_path):
+def test_same_results_and_errors_as_the_reference_on_the_same_files(h5, tmp_path):
+    """Against golden G20 (tools/gen_golden.py): what the reference's loadersaver returned, raised and wrote on the same files."""
+    g = golden("g20_losa_reference")
     path = str(tmp_path / "scan.nxs")
     _stack_file(h5, path)
     calls = [dict(key_path="entry/data/data"), dict(), dict(key_path="entry/data/data", index=3), dict(key_path="entry/data/data", index=3, axis=1),
              dict(key_path="entry/data/data", index=3, axis=2), dict(key_path="entry/data/data", index=(2, 7), axis=1),
              dict(key_path="entry/data/data", index=(1, 8, 3), axis=2), dict(key_path="entry/data/data", index=[0, 2, 5, 6]),
              dict(key_path="entry/data/data", index=(4, 5), axis=1), dict(key_path="entry/data/data", index=2, axis=7)]
-    for kw in calls:
-        want, got = ref_losa.load_hdf_file(path, **kw), losa.load_hdf_file(path, **kw)
+    for k, kw in enumerate(calls):
+        want, got = g["load_%d" % k], losa.load_hdf_file(path, **kw)
         assert want.dtype == got.dtype and want.shape == got.shape and np.array_equal(want, got), kw
-    for kw, fn in ((dict(key_path="nope"), "load_hdf_file"), (dict(key_path="entry/data/data", index=(3, 3)), "load_hdf_file"),
-                   (dict(key_path="entry/none"), "load_hdf_object")):
-        with pytest.raises(ValueError) as e_ref:
-            getattr(ref_losa, fn)(path, **kw)
+    for k, (kw, fn) in enumerate(((dict(key_path="nope"), "load_hdf_file"), (dict(key_path="entry/data/data", index=(3, 3)), "load_hdf_file"),
+                                  (dict(key_path="entry/none"), "load_hdf_object"))):
         with pytest.raises(ValueError) as e_own:
             getattr(losa, fn)(path, **kw)
-        assert str(e_ref.value) == str(e_own.value)
-    # files written by one side are read by the other
+        assert str(g["err_%d" % k]) == str(e_own.value)
+    # files written by one side are read by the other: the reference's file (its index and datasets, as it wrote them) is read
+    # here, and the file written here holds the same index and datasets -- what the reference read back from its own file
     vol = np.arange(2 * 3 * 4, dtype=np.float32).reshape(2, 3, 4)
-    a = ref_losa.save_hdf_file(str(tmp_path / "ref_out.h5"), vol, key_path="entry/x")
+    a = tmp_path / "ref_out.h5"
+    a.write_text(str(g["saved_index"]))
+    (tmp_path / "ref_out.h5.d").mkdir()
+    for key in g:
+        if key.startswith("saved_") and key[6:].isdigit():
+            np.save(str(tmp_path / "ref_out.h5.d" / (key[6:] + ".npy")), g[key])
     b = losa.save_hdf_file(str(tmp_path / "own_out.h5"), vol, key_path="entry/x")
-    assert np.array_equal(losa.load_hdf_file(str(a)), vol) and np.array_equal(ref_losa.load_hdf_file(str(b)), vol)
+    assert np.array_equal(losa.load_hdf_file(str(a)), vol) and np.array_equal(g["saved_read_back"], vol)
+    assert json.load(open(str(b))) == json.loads(str(g["saved_index"]))
+    for fname in sorted(os.listdir(str(b) + ".d")):
+        want = g["saved_" + fname[:-4]]
+        got = np.load(os.path.join(str(b) + ".d", fname))
+        assert want.dtype == got.dtype and want.shape == got.shape and np.array_equal(want, got), fname
     kw = dict(key_path="entry/data", data_type="int16", options={"entry/energy": 53})
-    da, db = ref_losa.open_hdf_stream(str(tmp_path / "ref_stream"), (2, 3, 4), **kw), losa.open_hdf_stream(str(tmp_path / "own_stream"), (2, 3, 4), **kw)
-    assert da.shape == db.shape and da.dtype == db.dtype and da.name == db.name
-    assert os.path.exists(str(tmp_path / "ref_stream.hdf")) and os.path.exists(str(tmp_path / "own_stream.hdf"))
-    with pytest.raises(ValueError) as e_ref:
-        ref_losa.open_hdf_stream(str(tmp_path / "r2.hdf"), (2, 2, 2), key_path="entry/data", options={"entry/data/angles": [1, 2]})
+    db = losa.open_hdf_stream(str(tmp_path / "own_stream"), (2, 3, 4), **kw)
+    assert db.shape == tuple(int(v) for v in g["stream_shape"]) and str(db.dtype) == str(g["stream_dtype"]) and db.name == str(g["stream_name"])
+    assert sorted(f.replace("own_", "ref_", 1) for f in os.listdir(str(tmp_path)) if f.startswith("own_stream")) == [str(f) for f in g["stream_files"]]
     with pytest.raises(ValueError) as e_own:
         losa.open_hdf_stream(str(tmp_path / "o2.hdf"), (2, 2, 2), key_path="entry/data", options={"entry/data/angles": [1, 2]})
-    assert str(e_ref.value) == str(e_own.value)
-    # images
+    assert str(g["err_stream"]) == str(e_own.value)
+    # images: the reference's files are read here as the reference reads them, and the files written here decode (PIL) to the
+    # same mode and pixels as the reference's -- so the reference reads them as it reads its own
+    from PIL import Image
     img = (noise(3, (40, 52)) * 1000.0).astype(np.float32)
-    for name in ("i.tif", "i.png", "i.jpg"):
-        pa, pb = ref_losa.save_image(str(tmp_path / ("ref_" + name)), img), losa.save_image(str(tmp_path / ("own_" + name)), img)
-        assert np.array_equal(ref_losa.load_image(str(pa)), losa.load_image(str(pb)))
-        assert np.array_equal(ref_losa.load_image(str(pb)), losa.load_image(str(pa)))
+    for ext in ("tif", "png", "jpg"):
+        pa = tmp_path / ("ref_i." + ext)
+        g["img_%s_file" % ext].tofile(str(pa))
+        pb = losa.save_image(str(tmp_path / ("own_i." + ext)), img)
+        want = g["img_%s_load" % ext]
+        assert np.array_equal(want, losa.load_image(str(pb))), ext
+        assert np.array_equal(want, losa.load_image(str(pa))), ext
+        with Image.open(str(pb)) as im:
+            assert im.mode == str(g["img_%s_mode" % ext]) and np.array_equal(np.array(im), g["img_%s_pil" % ext]), ext
 
 
 @pytest.mark.gpu

@@ -5,7 +5,7 @@
 #   tests         pytest -m gpu (the round-end suite)              smoke        __graft_entry__.smoke()
 #   profile       tools/profile.sh <tag>: rocprofv3 --kernel-trace --stats of the default bench command + the PMC passes
 #   profile_ordered  the same timing pass with --dispatch ordered (one stream: the kernel's average duration by itself)
-#   bench         python bench.py                                  bench_driver  the driver's command, --gpus 1 --steps 20 --warmup 5
+#   bench         python bench.py --full                           bench_driver  the driver's command, --gpus 1 --steps 20 --warmup 5 --full
 #   bench_ordered the driver's command with --dispatch ordered     dispatch     tools/time_dispatch.py (ordered / any-order / N streams / batch)
 #   spline        tools/time_spline_modes.py + per-kernel times    pmc_spline   tools/pmc_spline.sh
 #   fuzz          30 000 randomised cases against the oracle       fuzz_big     4 000 large frames       fuzz_pf2d  3 000 aimed at the spline prefilter
@@ -28,8 +28,8 @@ for s in $STEPS; do
     profile_ordered) PASSES="trace" bash tools/profile.sh ${TAG}_ordered --dispatch ordered > $O/profile_ordered.log 2>&1
              find gpurun_out/prof_${TAG}_ordered -name "*.csv" ! -name "out_kernel_stats.csv" -delete; find gpurun_out/prof_${TAG}_ordered -name "*.db" -delete
              head -8 gpurun_out/prof_${TAG}_ordered/summary.txt | cut -c1-200 ;;
-    bench) python bench.py > $O/bench_1gpu.json 2> $O/bench_1gpu.err; head -c 300 $O/bench_1gpu.json; echo ;;
-    bench_driver) python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; head -c 400 $O/bench_driver_cmd.json; echo ;;
+    bench) python bench.py --full > $O/bench_1gpu.json 2> $O/bench_1gpu.err; head -c 300 $O/bench_1gpu.json; echo ;;
+    bench_driver) python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; head -c 400 $O/bench_driver_cmd.json; echo ;;
     bench_ordered) python bench.py --gpus 1 --steps 20 --warmup 5 --dispatch ordered --no-extras --no-cpu-baseline > $O/bench_ordered.json 2> $O/bench_ordered.err; head -c 300 $O/bench_ordered.json; echo ;;
     dispatch) python tools/time_dispatch.py --rounds 3 --modes ordered,two_streams,streams3,any_order,batch > $O/dispatch_modes.txt 2>&1; tail -15 $O/dispatch_modes.txt ;;
     spline) python tools/time_spline_modes.py > $O/time_spline_modes.txt 2>&1; tail -30 $O/time_spline_modes.txt ;;

@@ -471,4 +471,61 @@ def g18():
 
 
 g18()
+
+
+# G20: the reference's losa/loadersaver on the files of tests/test_losa_hdf.py (h5py through tests/helpers/fake_h5py.py, images
+# through PIL): what it reads from a seeded stack file, the errors it raises, the file it writes (index + datasets), the stream it
+# opens, and the image files it writes (their bytes, PIL's decoding of them, and what its own load_image returns).
+def g20():
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import fake_h5py
+    sys.modules["h5py"] = fake_h5py
+    from PIL import Image
+    import discorpy.losa.loadersaver as ref
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "scan.nxs")
+        vol = (np.random.default_rng(5).random((9, 14, 11)) * 60000).astype(">u2")          # test_losa_hdf._stack_file
+        with fake_h5py.File(path, "w") as f:
+            f.create_dataset("entry/data/data", data=vol)
+            f.create_dataset("entry/angles", data=np.linspace(0.0, 180.0, 9))
+        calls = [dict(key_path="entry/data/data"), dict(), dict(key_path="entry/data/data", index=3),
+                 dict(key_path="entry/data/data", index=3, axis=1), dict(key_path="entry/data/data", index=3, axis=2),
+                 dict(key_path="entry/data/data", index=(2, 7), axis=1), dict(key_path="entry/data/data", index=(1, 8, 3), axis=2),
+                 dict(key_path="entry/data/data", index=[0, 2, 5, 6]), dict(key_path="entry/data/data", index=(4, 5), axis=1),
+                 dict(key_path="entry/data/data", index=2, axis=7)]
+        for k, kw in enumerate(calls):
+            out["load_%d" % k] = ref.load_hdf_file(path, **kw)
+        for k, (kw, fn) in enumerate(((dict(key_path="nope"), "load_hdf_file"), (dict(key_path="entry/data/data", index=(3, 3)), "load_hdf_file"),
+                                      (dict(key_path="entry/none"), "load_hdf_object"))):
+            try:
+                getattr(ref, fn)(path, **kw)
+            except ValueError as e:
+                out["err_%d" % k] = np.array(str(e))
+        v2 = np.arange(2 * 3 * 4, dtype=np.float32).reshape(2, 3, 4)
+        a = str(ref.save_hdf_file(os.path.join(td, "ref_out.h5"), v2, key_path="entry/x"))
+        out["saved_index"] = np.array(open(a).read())
+        for fname in sorted(os.listdir(a + ".d")):
+            out["saved_" + fname[:-4]] = np.load(os.path.join(a + ".d", fname))
+        out["saved_read_back"] = ref.load_hdf_file(a)
+        da = ref.open_hdf_stream(os.path.join(td, "ref_stream"), (2, 3, 4), key_path="entry/data", data_type="int16",
+                                 options={"entry/energy": 53})
+        out["stream_shape"], out["stream_dtype"], out["stream_name"] = np.array(da.shape), np.array(str(da.dtype)), np.array(da.name)
+        out["stream_files"] = np.array(sorted(f for f in os.listdir(td) if f.startswith("ref_stream")))
+        try:
+            ref.open_hdf_stream(os.path.join(td, "r2.hdf"), (2, 2, 2), key_path="entry/data", options={"entry/data/angles": [1, 2]})
+        except ValueError as e:
+            out["err_stream"] = np.array(str(e))
+        img = (np.random.default_rng(3).random((40, 52), dtype=np.float32) * 1000.0).astype(np.float32)      # conftest.noise(3, ...)
+        for ext in ("tif", "png", "jpg"):
+            p = str(ref.save_image(os.path.join(td, "ref_i." + ext), img))
+            out["img_%s_file" % ext] = np.fromfile(p, dtype=np.uint8)
+            with Image.open(p) as im:
+                out["img_%s_mode" % ext], out["img_%s_pil" % ext] = np.array(im.mode), np.array(im)
+            out["img_%s_load" % ext] = ref.load_image(p)
+    save("g20_losa_reference", **out)
+
+
+g20()
 print("done")

@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 (cd "$ROOT" && python -c "import bench; print(bench.kernel_sources_digest())" > "$OUT/kernel_sources.sha256" 2>/dev/null)
 export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $*"      # counter passes: the headline kernel only
-BENCH_FULL="python $ROOT/bench.py --no-cpu-baseline $*"    # the timing pass profiles the default command: headline + every other configuration
+BENCH_FULL="python $ROOT/bench.py --full --no-cpu-baseline $*"    # the timing pass: headline + every other configuration
 cd /tmp
 run() { # name, rocprof args...   (PASSES="trace fetch" restricts the passes that run)
   local name=$1; shift
