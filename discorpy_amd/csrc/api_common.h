@@ -111,6 +111,9 @@ struct HostStreams {
 extern thread_local HostStreams g_host_streams;
 
 bool host_direct_applies();      // api_image.cpp
+// The one reading of a mem_kind argument: *host = DCP_MEM_HOST.  DCP_MEM_DEVICE_UNORDERED is accepted where `unordered` is given
+// (device memory, *unordered = true); anything else is DCP_ERR_INVALID_ARG.
+int mem_kind_of(int mem_kind, bool* host, bool* unordered = nullptr);
 int sampler_of(int order, int blend_mode, int* sampler);
 int check_image(const void* src, const void* dst, int64_t H, int64_t W, int64_t rs, int64_t cs);
 int check_image_typed(const void* src, const void* dst, int dtype, int64_t H, int64_t W, int64_t rs, int64_t cs);
@@ -141,9 +144,75 @@ int frames_as_stack(const float* src0, float* dst0, int nframes, int64_t height,
 // api_spline.cpp: frees the coefficient planes of every device (waits for the devices first)
 int release_spline_workspace();
 
-// api_spline.cpp: orders 2..5 on any element type; map_kind 0 radial, 1 perspective, 2 explicit coordinates, 3 fused
-int run_spline(int map_kind, const void* src, void* dst, int dtype, int64_t H, int64_t W, int64_t rs, int64_t cs,
-               const dcp::MapArgs& map, const void* ycoord, const void* xcoord, int coord_dtype, int64_t npts, int order,
-               int mode, int mem_kind, int device, void* stream);
+static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPersp && DCP_MAP_FUSED == dcp::kFused, "map kinds");
+
+// One description of every single-frame call (api_image.cpp make_frame_call validates it, run_frame executes it), as StackCall
+// is of every stack call.  Executors: the tuned float32 kernels within 32-bit offsets (unwarp_kernels.hip), the generic ones for
+// orders 0 / 1 on any element type (typed_kernels.hip, or remap_wg_kernel / the one-channel colour kernel where they qualify),
+// interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip).
+enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline };
+struct FrameCall {
+  FrameExec exec;
+  dcp::MapKind kind;
+  dcp::MapArgs map;
+  const void* src;
+  void* dst;
+  int dtype;
+  int64_t H, W, rs, cs;            // strides in elements (interleaved channels: cs between pixels)
+  int channels;                    // 1 except for interleaved channels
+  const void* ycoord;              // kCoords: npts source coordinates, float32 or float64 (coord_dtype)
+  const void* xcoord;
+  int coord_dtype;
+  int64_t npts;
+  int order, sampler, mode, exact_sum, round_f32;
+  bool host;                       // DCP_MEM_HOST
+  int device;
+  hipStream_t stream;
+  dcp::LaunchOpts opts;            // current_opts() once per call; any_order only for device memory
+};
+
+// The staged round trip of a DCP_MEM_HOST call, on `st`: `src` goes up into staging slot 0 (`rows` rows of `row_bytes`, `pitch`
+// bytes apart on the host: one copy when pitch == row_bytes, else a 2-D copy that packs them), the planes y_up / x_up (`plane`
+// bytes each) into slots 2 / 3; launch(dsrc, ddst, dy, dx) enqueues the work; `out_bytes` come back from slot 1 into `dst`, and
+// slots 2 / 3 into y_down / x_down (a coordinate map); then `st` is synchronised.
+struct HostTrip {
+  const void* src = nullptr;
+  size_t row_bytes = 0, rows = 1, pitch = 0;
+  const void* y_up = nullptr;
+  const void* x_up = nullptr;
+  void* y_down = nullptr;
+  void* x_down = nullptr;
+  size_t plane = 0;
+  void* dst = nullptr;
+  size_t out_bytes = 0;
+};
+template <typename Launch>
+int host_round_trip(const HostTrip& t, hipStream_t st, Launch&& launch) {
+  void *dsrc = nullptr, *ddst = nullptr, *dy = nullptr, *dx = nullptr;
+  if (t.src) DCP_HIP(g_staging.get(0, t.rows * t.row_bytes, &dsrc));
+  if (t.dst) DCP_HIP(g_staging.get(1, t.out_bytes, &ddst));
+  if (t.plane) {
+    DCP_HIP(g_staging.get(2, t.plane, &dy));
+    DCP_HIP(g_staging.get(3, t.plane, &dx));
+  }
+  if (t.src && t.pitch == t.row_bytes) DCP_HIP(hipMemcpyAsync(dsrc, t.src, t.rows * t.row_bytes, hipMemcpyHostToDevice, st));
+  if (t.src && t.pitch != t.row_bytes)
+    DCP_HIP(hipMemcpy2DAsync(dsrc, t.row_bytes, t.src, t.pitch, t.row_bytes, t.rows, hipMemcpyHostToDevice, st));
+  if (t.y_up) {
+    DCP_HIP(hipMemcpyAsync(dy, t.y_up, t.plane, hipMemcpyHostToDevice, st));
+    DCP_HIP(hipMemcpyAsync(dx, t.x_up, t.plane, hipMemcpyHostToDevice, st));
+  }
+  DCP_HIP(launch(dsrc, ddst, dy, dx));
+  if (t.dst) DCP_HIP(hipMemcpyAsync(t.dst, ddst, t.out_bytes, hipMemcpyDeviceToHost, st));
+  if (t.y_down) {
+    DCP_HIP(hipMemcpyAsync(t.y_down, dy, t.plane, hipMemcpyDeviceToHost, st));
+    DCP_HIP(hipMemcpyAsync(t.x_down, dx, t.plane, hipMemcpyDeviceToHost, st));
+  }
+  DCP_HIP(hipStreamSynchronize(st));
+  return DCP_OK;
+}
+
+// api_spline.cpp: the spline executor (c.exec == kExecSpline; the device is selected)
+int run_spline(const FrameCall& c);
 
 }  // namespace dcpapi

@@ -49,6 +49,13 @@ dcp::LaunchOpts current_opts() {
 thread_local Staging g_staging;
 thread_local HostStreams g_host_streams;
 
+int mem_kind_of(int mem_kind, bool* host, bool* unordered) {
+  *host = mem_kind == DCP_MEM_HOST;
+  if (unordered) *unordered = mem_kind == DCP_MEM_DEVICE_UNORDERED;
+  if (mem_kind == DCP_MEM_HOST || mem_kind == DCP_MEM_DEVICE || (unordered && *unordered)) return DCP_OK;
+  return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
+}
+
 int sampler_of(int order, int blend_mode, int* sampler) {
   if (order == 0) {
     *sampler = dcp::kNearest;

@@ -1,19 +1,15 @@
-// api_image.cpp -- whole-image entry points of the C ABI: radial / perspective / fused remaps, explicit
-// coordinates and coordinate maps for float32 (tuned kernels, unwarp_kernels.hip), the same for the other
-// element types and interleaved channels (typed_kernels.hip; orders >= 2 go to api_spline.cpp).
+// api_image.cpp -- single-frame entry points of the C ABI: radial / perspective / fused remaps, explicit coordinates,
+// interleaved channels, points and coordinate maps, on float32 and the other element types, orders 0..5.  Every frame call
+// is described once (FrameCall, make_frame_call) and executed by run_frame; spline orders by api_spline.cpp's run_spline.
 #include "api_common.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 #include <algorithm>
-#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
-#include <vector>
 #include <thread>
 #include <vector>
 
@@ -30,18 +26,9 @@ bool beyond_32bit_offsets(int64_t H, int64_t W, int64_t rs, int64_t cs) {
   return extent > 4294967040.0 && H <= 1073741823LL && W <= 1073741823LL;
 }
 
-int run_typed(int map_kind, const void* src, void* dst, int dtype, int64_t H, int64_t W, int64_t rs, int64_t cs,
-              const dcp::MapArgs& map, const void* ycoord, const void* xcoord, int coord_dtype, int64_t npts, int order,
-              int mode, int mem_kind, int device, void* stream);
-
 // Does this HIP runtime move pageable data in both PCIe directions at once when two host threads copy on two
 // streams?  ROCm 7.2's does (45 GB/s each way); the runtime bundled with PyTorch-ROCm 2.10 serialises the two
 // directions, and the banded path then only adds overhead.  Measured once per process on 32 MiB buffers.
-// (dcp_get_option("host_direct_applies"): would a registered float32 host destination be written directly?  The Python pool
-// pins its blocks only then)
-bool runtime_overlaps_directions();
-bool host_direct_applies_here() { return g_host_direct.load() && (g_host_direct.load() == 2 || !g_host_duplex.load() || !runtime_overlaps_directions()); }
-
 bool runtime_overlaps_directions() {
   static std::once_flag once;
   static bool overlaps = false;
@@ -300,288 +287,337 @@ int run_host_direct(const void* src, void* dst_alias, int64_t H, int64_t W, size
   return DCP_OK;
 }
 
-// Shared driver of the three whole-image entry points.
-int run_image(dcp::MapKind kind, const float* src, float* dst, int64_t H, int64_t W, int64_t rs, int64_t cs,
-              const dcp::MapArgs& map, int sampler, bool round_f32, int mem_kind, int device, void* stream) {
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  dcp::ImageArgs img;
-  memset(&img, 0, sizeof(img));
-  img.H = (int32_t)H;
-  img.W = (int32_t)W;
-  dcp::LaunchOpts opts = current_opts();
-  if (mem_kind == DCP_MEM_DEVICE_UNORDERED) {      // device pointers, and the launch need not wait for earlier work of `stream`
-    opts.any_order = 1;
-    mem_kind = DCP_MEM_DEVICE;
+// Source rows [*b0, *b1) that output rows [r0, r0 + n) of a radial, perspective or fused map can reach (the bands of
+// run_host_banded / run_host_direct).  The homography of a banded frame has a denominator of one sign over the frame ("tame",
+// MapArgs::fast_div): its position is monotone along every segment, so over a band of output rows it takes its extremes at the
+// band's four corners; the fused map then evaluates the radial model inside that clipped rectangle of positions.
+void band_source_rows(dcp::MapKind kind, const dcp::MapArgs& map, int64_t H, int64_t W, int64_t r0, int64_t n, int64_t* b0,
+                      int64_t* b1) {
+  if (kind == dcp::kRadial) {
+    host_row_band(map, H, W, (double)r0, n, b0, b1);
+    return;
   }
-  if (mem_kind == DCP_MEM_DEVICE) {
-    img.src = src;
-    img.dst = dst;
-    img.src_stride = (int32_t)rs;
-    img.src_col_stride = (int32_t)cs;
-    img.src_bytes = extent_bytes(H, W, rs, cs);
-    DCP_HIP(dcp::launch_image(kind, img, map, sampler, round_f32, opts, (hipStream_t)stream));
-    return DCP_OK;
+  double ylo = 1e300, yhi = -1e300, xlo = 1e300, xhi = -1e300;
+  for (double y : {(double)r0, (double)(r0 + n - 1)})
+    for (double x : {0.0, (double)(W - 1)}) {
+      const double den = (map.coef[6] * x + map.coef[7] * y) + 1.0;
+      double yd = ((map.coef[3] * x + map.coef[4] * y) + map.coef[5]) / den;
+      double xd = ((map.coef[0] * x + map.coef[1] * y) + map.coef[2]) / den;
+      if (!(yd >= 0.0)) yd = 0.0;
+      if (yd > (double)(H - 1)) yd = (double)(H - 1);
+      if (!(xd >= 0.0)) xd = 0.0;
+      if (xd > (double)(W - 1)) xd = (double)(W - 1);
+      ylo = std::min(ylo, yd);
+      yhi = std::max(yhi, yd);
+      xlo = std::min(xlo, xd);
+      xhi = std::max(xhi, xd);
+    }
+  if (kind == dcp::kFused) {
+    // float32 rounding of the perspective position moves it by < 1e-3 px: widen the rectangle a little
+    host_row_band_rect(map, H, xlo - 0.01, xhi + 0.01, ylo - 0.01, yhi + 0.01, b0, b1);
+    return;
   }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  // a destination the GPU can address: the kernels write into it directly (run_host_direct)
-  // (taken where the runtime cannot run an upload and a download at once -- the one bundled with PyTorch-ROCm: 2.16 ms against
-  // 2.44 per 4096^2 frame; where it can -- /opt/rocm's -- the two-copy banded path below is the faster one, 1.78 ms against 2.15.
-  // "host_direct" = 2 forces it, 0 forbids it)
-  void* dst_alias = nullptr;
-  if (g_host_direct.load() && cs == 1 && H >= 512 && W >= 2 && (double)H * (double)W * 4.0 >= 16.0 * 1048576.0 &&
-      (double)H * (double)W * 4.0 <= 4294967040.0 && (kind == dcp::kRadial || map.fast_div) &&
-      (g_host_direct.load() == 2 || !g_host_duplex.load() || !runtime_overlaps_directions()))
-    dst_alias = registered_host_alias(dst, (size_t)H * (size_t)W * sizeof(float));
-  if (dst_alias) {
-    auto band_rows = [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) {
-      if (kind == dcp::kRadial) {
-        host_row_band(map, H, W, (double)r0, n, b0, b1);
-        return;
-      }
-      // homography with a denominator of one sign over the frame: the extremes of a band of rows are at its four corners
-      double ylo = 1e300, yhi = -1e300, xlo = 1e300, xhi = -1e300;
-      for (double y : {(double)r0, (double)(r0 + n - 1)})
-        for (double x : {0.0, (double)(W - 1)}) {
-          const double den = (map.coef[6] * x + map.coef[7] * y) + 1.0;
-          double yd = ((map.coef[3] * x + map.coef[4] * y) + map.coef[5]) / den;
-          double xd = ((map.coef[0] * x + map.coef[1] * y) + map.coef[2]) / den;
-          if (!(yd >= 0.0)) yd = 0.0;
-          if (yd > (double)(H - 1)) yd = (double)(H - 1);
-          if (!(xd >= 0.0)) xd = 0.0;
-          if (xd > (double)(W - 1)) xd = (double)(W - 1);
-          ylo = std::min(ylo, yd);
-          yhi = std::max(yhi, yd);
-          xlo = std::min(xlo, xd);
-          xhi = std::max(xhi, xd);
-        }
-      if (kind == dcp::kFused) {
-        host_row_band_rect(map, H, xlo - 0.01, xhi + 0.01, ylo - 0.01, yhi + 0.01, b0, b1);
-        return;
-      }
-      *b0 = std::max<int64_t>(0, (int64_t)std::floor(ylo) - 1);
-      *b1 = std::min<int64_t>(H, (int64_t)std::floor(yhi) + 3);
-    };
-    return run_host_direct(src, dst_alias, H, W, sizeof(float), (size_t)rs * sizeof(float), band_rows,
-                           [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
-                             dcp::ImageArgs b;
-                             memset(&b, 0, sizeof(b));
-                             b.H = (int32_t)H;
-                             b.W = (int32_t)W;
-                             b.src = (const float*)dsrc;
-                             b.dst = (float*)dband;
-                             b.src_stride = (int32_t)W;
-                             b.src_col_stride = 1;
-                             b.src_bytes = (uint32_t)((size_t)H * (size_t)W * 4);
-                             b.y_origin = (int32_t)r0;
-                             b.rows_out = (int32_t)n;
-                             return dcp::launch_image(kind, b, map, sampler, round_f32, opts, s);
-                           });
-  }
-  if ((kind == dcp::kPersp || kind == dcp::kFused) && map.fast_div && cs == 1 && H >= 512 && W >= 2 && g_host_duplex.load() &&
-      (double)H * (double)W * 4.0 >= 16.0 * 1048576.0 && (double)H * (double)W * 4.0 <= 4294967040.0 &&
-      (g_host_duplex.load() == 2 || runtime_overlaps_directions())) {
-    // homography with a denominator of one sign over the frame ("tame", checked by the caller): yd is monotone along
-    // every segment, so over a band of output rows it takes its extremes at the band's four corners
-    // (the same holds for xd; the fused map then evaluates the radial model inside that clipped rectangle of positions)
-    auto band = [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) {
-      double ylo = 1e300, yhi = -1e300, xlo = 1e300, xhi = -1e300;
-      for (double y : {(double)r0, (double)(r0 + n - 1)})
-        for (double x : {0.0, (double)(W - 1)}) {
-          const double den = (map.coef[6] * x + map.coef[7] * y) + 1.0;
-          double yd = ((map.coef[3] * x + map.coef[4] * y) + map.coef[5]) / den;
-          double xd = ((map.coef[0] * x + map.coef[1] * y) + map.coef[2]) / den;
-          if (!(yd >= 0.0)) yd = 0.0;
-          if (yd > (double)(H - 1)) yd = (double)(H - 1);
-          if (!(xd >= 0.0)) xd = 0.0;
-          if (xd > (double)(W - 1)) xd = (double)(W - 1);
-          ylo = std::min(ylo, yd);
-          yhi = std::max(yhi, yd);
-          xlo = std::min(xlo, xd);
-          xhi = std::max(xhi, xd);
-        }
-      if (kind == dcp::kFused) {
-        // float32 rounding of the perspective position moves it by < 1e-3 px: widen the rectangle a little
-        host_row_band_rect(map, H, xlo - 0.01, xhi + 0.01, ylo - 0.01, yhi + 0.01, b0, b1);
-        return;
-      }
-      *b0 = std::max<int64_t>(0, (int64_t)std::floor(ylo) - 1);
-      *b1 = std::min<int64_t>(H, (int64_t)std::floor(yhi) + 3);
-    };
-    return run_host_banded(src, dst, H, W, sizeof(float), (size_t)rs * sizeof(float), band,
-                           [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
-                             dcp::ImageArgs b;
-                             memset(&b, 0, sizeof(b));
-                             b.H = (int32_t)H;
-                             b.W = (int32_t)W;
-                             b.src = (const float*)dsrc;
-                             b.dst = (float*)dband;
-                             b.src_stride = (int32_t)W;
-                             b.src_col_stride = 1;
-                             b.src_bytes = (uint32_t)((size_t)H * (size_t)W * 4);
-                             b.y_origin = (int32_t)r0;
-                             b.rows_out = (int32_t)n;
-                             return dcp::launch_image(kind, b, map, sampler, round_f32, opts, s);
-                           });
-  }
-  if (kind == dcp::kRadial && sampler != dcp::kNearest && round_f32 && cs == 1 && H >= 512 && W >= 2 && g_host_duplex.load() &&
-      (double)H * (double)W * 4.0 >= 16.0 * 1048576.0 && (double)H * (double)W * 4.0 <= 4294967040.0 &&
-      (g_host_duplex.load() == 2 || runtime_overlaps_directions()))
-    return run_host_banded(src, dst, H, W, sizeof(float), (size_t)rs * sizeof(float),
-                                  [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) { host_row_band(map, H, W, (double)r0, n, b0, b1); },
-                                  [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
-                                    // a band of image rows = a chunk of rows of a one-projection stack
-                                    dcp::StackArgs st;
-                                    memset(&st, 0, sizeof(st));
-                                    st.D = 1;
-                                    st.H = (int32_t)H;
-                                    st.W = (int32_t)W;
-                                    st.row_start = (double)r0;
-                                    st.nrows = (int32_t)n;
-                                    st.vol = (const float*)dsrc;
-                                    st.out = (float*)dband;
-                                    st.proj_stride = H * W;
-                                    st.row_stride = (int32_t)W;
-                                    st.proj_bytes = (uint32_t)((size_t)H * (size_t)W * 4);
-                                    return dcp::launch_stack(st, map, sampler, true, opts, s);
-                                  });
-  // host memory: pack rows densely on the way in, run on the stream, copy back, synchronise
-  hipStream_t st = (hipStream_t)stream;
-  void *dsrc = nullptr, *ddst = nullptr;
-  const size_t frame = (size_t)H * (size_t)W * sizeof(float);
-  DCP_HIP(g_staging.get(0, frame, &dsrc));
-  DCP_HIP(g_staging.get(1, frame, &ddst));
-  if (cs == 1 && rs == W) {
-    DCP_HIP(hipMemcpyAsync(dsrc, src, frame, hipMemcpyHostToDevice, st));
-    img.src_stride = (int32_t)W;
-    img.src_col_stride = 1;
-    img.src_bytes = (uint32_t)frame;
-  } else if (cs == 1) {
-    DCP_HIP(hipMemcpy2DAsync(dsrc, (size_t)W * 4, src, (size_t)rs * 4, (size_t)W * 4, (size_t)H, hipMemcpyHostToDevice, st));
-    img.src_stride = (int32_t)W;
-    img.src_col_stride = 1;
-    img.src_bytes = (uint32_t)frame;
-  } else {
-    // column-strided host view (e.g. one channel of an interleaved HxWxC image): ship the
-    // enclosing extent and let the kernel's strided gather pick the channel
-    const size_t ext = extent_bytes(H, W, rs, cs);
-    DCP_HIP(g_staging.get(0, ext, &dsrc));
-    DCP_HIP(hipMemcpyAsync(dsrc, src, ext, hipMemcpyHostToDevice, st));
-    img.src_stride = (int32_t)rs;
-    img.src_col_stride = (int32_t)cs;
-    img.src_bytes = (uint32_t)ext;
-  }
-  img.src = (const float*)dsrc;
-  img.dst = (float*)ddst;
-  DCP_HIP(dcp::launch_image(kind, img, map, sampler, round_f32, opts, st));
-  DCP_HIP(hipMemcpyAsync(dst, ddst, frame, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
+  *b0 = std::max<int64_t>(0, (int64_t)std::floor(ylo) - 1);
+  *b1 = std::min<int64_t>(H, (int64_t)std::floor(yhi) + 3);
+}
+
+// How a DCP_MEM_HOST frame goes through the GPU.  A large one -- at least kBandRows rows and kBandBytes -- that its executor can run
+// in bands of rows travels in bands with uploads and downloads overlapped (run_host_banded, `banded_ok`) where the runtime runs the
+// two directions at once (/opt/rocm's: 1.78 ms against 2.15 for the direct path per 4096^2 frame); where it cannot (the one
+// bundled with PyTorch-ROCm: 2.16 ms against 2.44) the kernels write into a registered destination directly (run_host_direct,
+// `direct_ok`).  "host_direct" / "host_duplex" = 2 force these paths, 0 forbid them.  Everything else is staged whole.
+// *alias = the device address of `dst` for kDirect; alias == nullptr asks whether a registered destination would be written directly.
+enum HostPath { kStaged, kBanded, kDirect };
+constexpr int64_t kBandRows = 512;
+constexpr double kBandBytes = 16.0 * 1048576.0;
+bool large_host_frame(int64_t H, double bytes) { return H >= kBandRows && bytes >= kBandBytes; }
+HostPath host_path(int64_t H, double bytes, bool direct_ok, bool banded_ok, const void* dst, void** alias) {
+  if (!large_host_frame(H, bytes)) return kStaged;
+  if (direct_ok && g_host_direct.load() && (g_host_direct.load() == 2 || !g_host_duplex.load() || !runtime_overlaps_directions()) &&
+      (!alias || (*alias = registered_host_alias(dst, (size_t)bytes))))
+    return kDirect;
+  if (banded_ok && g_host_duplex.load() && (g_host_duplex.load() == 2 || runtime_overlaps_directions())) return kBanded;
+  return kStaged;
+}
+
+// The map of a frame call: a perspective or fused map needs its homography, flagged tame (fast_div) over an H x W frame;
+// a perspective map takes no radial coefficients, kCoords no map at all.
+int frame_map(dcp::MapArgs* m, dcp::MapKind kind, double xc, double yc, const double* fact, int nfact, const double* coef, int64_t H,
+              int64_t W) {
+  const bool homography = kind == dcp::kPersp || kind == dcp::kFused, radial = kind == dcp::kRadial || kind == dcp::kFused;
+  if (homography && !coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
+  if (const int rc = fill_map(m, xc, yc, radial ? fact : nullptr, radial ? nfact : 0, homography ? coef : nullptr)) return rc;
+  if (homography && H > 0 && W > 0) m->fast_div = homography_is_tame(coef, H, W);
   return DCP_OK;
 }
 
-// Orders 0..5 on any element type: 0/1 through typed_kernels.hip, 2..5 through the spline path.
-// map_kind 0 radial, 1 perspective, 2 fused, 3 explicit coordinates.
-int run_typed(int map_kind, const void* src, void* dst, int dtype, int64_t H, int64_t W, int64_t rs, int64_t cs,
-              const dcp::MapArgs& map, const void* ycoord, const void* xcoord, int coord_dtype, int64_t npts, int order,
-              int mode, int mem_kind, int device, void* stream) {
+int check_coords(const FrameCall& c) {
+  if (c.kind != dcp::kCoords) return DCP_OK;
+  if (c.npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
+  if (c.npts > 0 && (!c.ycoord || !c.xcoord)) return fail(DCP_ERR_INVALID_ARG, "null coordinate pointer");
+  if (c.coord_dtype != DCP_COORD_F32 && c.coord_dtype != DCP_COORD_F64) return fail(DCP_ERR_INVALID_ARG, "unknown coord_dtype %d", c.coord_dtype);
+  if (c.exec != kExecSpline && c.npts > 2147483647LL * 256) return fail(DCP_ERR_UNSUPPORTED, "too many points");
+  return DCP_OK;
+}
+
+struct Points {      // kCoords: npts source coordinates (y, x), float32 or float64 (dtype = DCP_COORD_*)
+  const void* y;
+  const void* x;
+  int dtype;
+  int64_t npts;
+};
+
+// Fills and validates *c, before any device work.  `exec` is the executor the entry point names; a tuned float32 call whose source
+// lies beyond 32-bit offsets moves to the generic kernels, a generic call of order 2..5 to the spline path.
+int make_frame_call(FrameCall* c, FrameExec exec, dcp::MapKind kind, const void* src, void* dst, int dtype, int64_t H, int64_t W,
+                    int64_t rs, int64_t cs, int channels, double xc, double yc, const double* fact, int nfact, const double* coef,
+                    Points pts, int order, int blend_mode, int mode, int round_f32, int mem_kind, int device, void* stream) {
   int rc;
-  if (order < 0 || order > 5) return fail(DCP_ERR_INVALID_ARG, "spline order %d outside [0, 5]", order);
-  if (mode < 0 || (mode & ~DCP_SPLINE_SCIPY_SUM) > 7) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
-  if (order < 2) mode &= ~DCP_SPLINE_SCIPY_SUM;        // (orders 0 / 1 of the typed entry points always blend in scipy's order)
-  if (order >= 2) {   // run_spline numbers the maps 0 radial, 1 perspective, 2 coordinates, 3 fused
-    return run_spline(map_kind == 3 ? 2 : map_kind == 2 ? 3 : map_kind, src, dst, dtype, H, W, rs, cs, map, ycoord, xcoord, coord_dtype, npts,
-                      order, mode, mem_kind, device, stream);
+  // DCP_MEM_DEVICE_UNORDERED: the tuned whole-image entry points only.  A launch leaves unordered only on device memory: a host
+  // call's kernels sit right behind its own uploads, whatever the lab switch "x_any_order" says
+  bool unordered = false;
+  if ((rc = mem_kind_of(mem_kind, &c->host, exec == kExecTuned && kind != dcp::kCoords ? &unordered : nullptr)) != DCP_OK) return rc;
+  c->opts = current_opts();
+  if (c->host || unordered) c->opts.any_order = unordered;
+  if ((rc = frame_map(&c->map, kind, xc, yc, fact, nfact, coef, H, W)) != DCP_OK) return rc;
+  c->exec = exec;
+  c->kind = kind;
+  c->src = src;
+  c->dst = dst;
+  c->dtype = dtype;
+  c->H = H;
+  c->W = W;
+  c->rs = rs;
+  c->cs = cs;
+  c->channels = channels;
+  c->ycoord = pts.y;
+  c->xcoord = pts.x;
+  c->coord_dtype = pts.dtype;
+  c->npts = pts.npts;
+  c->order = order;
+  c->sampler = dcp::kScipy;
+  c->mode = mode;
+  c->exact_sum = 0;
+  c->round_f32 = round_f32 != 0;
+  c->device = device;
+  c->stream = (hipStream_t)stream;
+  const bool cert = g_tile_cert.load() != 0;
+  if (exec == kExecColour) {
+    if (channels < 1 || channels > 64) return fail(DCP_ERR_INVALID_ARG, "channels = %d outside [1, 64]", channels);
+    if (order < 0 || order > 1) return fail(DCP_ERR_UNSUPPORTED, "the interleaved-channel kernels take orders 0 and 1 (got %d)", order);
+    if (blend_mode != DCP_BLEND_SCIPY && blend_mode != DCP_BLEND_F64LERP)
+      return fail(DCP_ERR_UNSUPPORTED, "interleaved channels blend as scipy does (DCP_BLEND_SCIPY) or within one ulp of it (DCP_BLEND_F64LERP); got %d", blend_mode);
+    if (cs < channels) return fail(DCP_ERR_INVALID_ARG, "pixel stride %lld smaller than %d channels", (long long)cs, channels);
+    if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
+    if (rs < (W - 1) * cs + channels && H > 1)
+      return fail(DCP_ERR_INVALID_ARG, "row stride %lld overlaps rows of %lld pixels", (long long)rs, (long long)W);
+    // float32 only: the one-ulp factorisation; integer types always blend in scipy's exact order (their rounding ties depend on it)
+    c->sampler = order == 0 ? dcp::kNearest : (blend_mode == DCP_BLEND_F64LERP && dtype == dcp::kF32 ? dcp::kF64Lerp : dcp::kScipy);
+    c->map.tile_dev_ok = cert ? tile_deviation_certified(dcp::kRadial, c->map, H, W) : 0;
+    return DCP_OK;
+  }
+  if (exec == kExecTuned) {
+    if (kind == dcp::kCoords && (mode < 0 || mode > 7)) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
+    if ((rc = sampler_of(order, blend_mode, &c->sampler)) != DCP_OK) return rc;
+    if (!(round_f32 && beyond_32bit_offsets(H, W, rs, cs))) {
+      if ((rc = check_image(src, dst, H, W, rs, cs)) != DCP_OK) return rc;
+      if (cert && kind != dcp::kCoords && (kind != dcp::kFused || g_fused_wg.load())) {
+        int tall = 0;
+        c->map.tile_dev_ok = tile_deviation_certified(kind, c->map, H, W, kind == dcp::kRadial ? &tall : nullptr);
+        c->map.tall_ok = tall;
+      }
+      return check_coords(*c);
+    }
+    c->exec = exec = kExecTyped;
+  }
+  if (exec == kExecTyped) {
+    if (order < 0 || order > 5) return fail(DCP_ERR_INVALID_ARG, "spline order %d outside [0, 5]", order);
+    if (mode < 0 || (mode & ~DCP_SPLINE_SCIPY_SUM) > 7) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
+    if (order < 2) {
+      c->mode = mode & ~DCP_SPLINE_SCIPY_SUM;        // (orders 0 / 1 of the typed entry points always blend in scipy's order)
+      if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
+      return check_coords(*c);
+    }
+    c->exec = kExecSpline;
   }
   if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
-  if (map_kind == 3) {
-    if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
-    if (npts > 0 && (!ycoord || !xcoord)) return fail(DCP_ERR_INVALID_ARG, "null coordinate pointer");
-    if (coord_dtype != DCP_COORD_F32 && coord_dtype != DCP_COORD_F64) return fail(DCP_ERR_INVALID_ARG, "unknown coord_dtype %d", coord_dtype);
-    if (npts > 2147483647LL * 256) return fail(DCP_ERR_UNSUPPORTED, "too many points");
-    if (npts == 0) return DCP_OK;
+  if (order < 2 || order > 5) return fail(DCP_ERR_INVALID_ARG, "spline order %d outside [2, 5]", order);
+  // bit 8 of boundary_mode (DCP_SPLINE_SCIPY_SUM): accumulate the taps in scipy's operation order instead of the factorised sum
+  c->exact_sum = (mode >= 0 && (mode & DCP_SPLINE_SCIPY_SUM)) ? 1 : 0;
+  if (mode >= 0) c->mode = mode &= ~DCP_SPLINE_SCIPY_SUM;
+  if (mode < 0 || mode > 7) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
+  if ((rc = check_coords(*c)) != DCP_OK) return rc;
+  if (H > 1000000 || W > 1000000) return fail(DCP_ERR_UNSUPPORTED, "image too large for the spline path");
+  // the host's tile-deviation certificate lets the gather stage its taps in LDS (spline_wg_kernel)
+  if (cert && (kind == dcp::kRadial || kind == dcp::kPersp)) c->map.tile_dev_ok = tile_deviation_certified(kind, c->map, H, W);
+  return DCP_OK;
+}
+
+// Output rows [y0, y0 + rows) of the frame (rows = 0: all of it) from the source at `src` (strides rs / cs in elements; kCoords:
+// the points at y / x) into `dst` on stream `s`: the launch of every memory path of run_frame.
+hipError_t launch_frame(const FrameCall& c, const void* src, void* dst, const void* y, const void* x, int64_t rs, int64_t cs, int64_t y0,
+                        int64_t rows, hipStream_t s) {
+  dcp::ImageArgs img;
+  memset(&img, 0, sizeof(img));
+  img.H = (int32_t)c.H;
+  img.W = (int32_t)c.W;
+  img.src = (const float*)src;
+  img.dst = (float*)dst;
+  img.src_stride = (int32_t)rs;
+  img.src_col_stride = (int32_t)cs;
+  dcp::CoordArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.ycoord = y;
+  ca.xcoord = x;
+  ca.npts = c.npts;
+  ca.is_f64 = c.coord_dtype == DCP_COORD_F64;
+  ca.mode = c.mode;
+  if (c.exec == kExecTuned) {
+    img.src_bytes = extent_bytes(c.H, c.W, rs, cs);
+    img.y_origin = (int32_t)y0;
+    img.rows_out = (int32_t)rows;
+    if (c.kind == dcp::kCoords) return dcp::launch_coords(img, ca, c.sampler, s);
+    return dcp::launch_image(c.kind, img, c.map, c.sampler, c.round_f32 != 0, c.opts, s);
   }
+  dcp::TypedImageArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src;
+  a.dst = dst;
+  a.H = (int32_t)c.H;
+  a.W = (int32_t)c.W;
+  a.src_stride = rs;
+  a.src_cstride = cs;
+  a.order = c.order;
+  a.dtype = c.dtype;
+  bool taken = false;
+  if (c.exec == kExecColour) {
+    // the workgroup-box kernel (remap_wg_color_kernel) where the call qualifies -- dense pixels of 3 / 4 channels, float32 / uint8 /
+    // uint16, certified map --, else one thread per pixel
+    const double ext = ((double)(c.H - 1) * (double)rs + (double)(c.W - 1) * (double)cs + (double)c.channels) * (double)dcp::elem_size(c.dtype);
+    a.blend = c.sampler;
+    a.y0 = (int32_t)y0;
+    a.rows = (int32_t)(rows ? rows : c.H);
+    if (ext <= 4294900000.0 && rs < (1ll << 31)) {
+      img.src_bytes = (uint32_t)ext;
+      img.y_origin = a.y0;
+      img.rows_out = a.rows;
+      const hipError_t e = dcp::launch_color(img, c.map, c.channels, c.dtype, c.sampler, c.opts, s, &taken);
+      if (e != hipSuccess || taken) return e;
+    }
+    return dcp::launch_typed_channels(a, c.map, c.channels, s);
+  }
+  // 8- / 16-bit integers, radial or perspective map, certified: the workgroup-box kernel (same arithmetic, LDS-staged); 4- and
+  // 8-byte element types under a radial map: the interleaved-pixel kernel with one channel (color_kernels.hip)
+  if ((c.kind == dcp::kRadial || c.kind == dcp::kPersp) && cs == 1 && (double)extent_bytes_typed(c.H, c.W, rs, 1, c.dtype) <= 4294900000.0) {
+    dcp::MapArgs mapc = c.map;
+    mapc.tile_dev_ok = g_tile_cert.load() ? tile_deviation_certified(c.kind, mapc, c.H, c.W) : 0;
+    if (c.kind == dcp::kPersp) mapc.fast_div = homography_is_tame(mapc.coef, c.H, c.W);
+    img.src_bytes = (uint32_t)extent_bytes_typed(c.H, c.W, rs, 1, c.dtype);
+    img.xcd_remap = c.opts.xcd_remap;
+    const hipError_t e = c.kind == dcp::kRadial && (c.dtype == dcp::kF64 || c.dtype == dcp::kI32 || c.dtype == dcp::kU32)
+                             ? dcp::launch_color(img, mapc, 1, c.dtype, c.order == 0 ? dcp::kNearest : dcp::kScipy, c.opts, s, &taken)
+                             : dcp::launch_wg_typed(c.kind, img, mapc, c.order, c.dtype, c.opts, s, &taken);
+    if (e != hipSuccess || taken) return e;
+  }
+  return dcp::launch_typed_image(c.kind, a, c.map, ca, s);
+}
+
+// Executes a validated FrameCall: device memory in one launch on the caller's stream; host memory in bands (large dense frames
+// of the tuned image kernels and of interleaved channels, host_path) or staged whole.
+int run_frame(const FrameCall& c) {
+  if (c.kind == dcp::kCoords && c.npts == 0) return DCP_OK;
+  DeviceScope scope(c.device);
+  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", c.device, hipGetErrorString(scope.status));
+  if (c.exec == kExecSpline) return run_spline(c);
+  if (!c.host) {
+    DCP_HIP(launch_frame(c, c.src, c.dst, c.ycoord, c.xcoord, c.rs, c.cs, 0, 0, c.stream));
+    return DCP_OK;
+  }
+  const size_t esz = (size_t)dcp::elem_size(c.dtype), pix = (size_t)c.channels * esz;
+  const bool tuned_image = c.exec == kExecTuned && c.kind != dcp::kCoords;
+  if (tuned_image || c.exec == kExecColour) {
+    const bool dense = tuned_image ? c.cs == 1 && c.W >= 2 : c.cs == c.channels;
+    // radial float32 bands go through the stack kernel (a band of image rows = a chunk of rows of a one-projection stack)
+    const bool stack_bands = tuned_image && c.kind == dcp::kRadial && c.sampler != dcp::kNearest && c.round_f32;
+    void* alias = nullptr;
+    const HostPath path = host_path(c.H, (double)c.H * (double)c.W * (double)pix, dense && tuned_image && (c.kind == dcp::kRadial || c.map.fast_div),
+                                    dense && (!tuned_image || stack_bands || (c.kind != dcp::kRadial && c.map.fast_div)), c.dst, &alias);
+    auto hull = [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) { band_source_rows(c.kind, c.map, c.H, c.W, r0, n, b0, b1); };
+    auto band = [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
+      return launch_frame(c, dsrc, dband, nullptr, nullptr, c.W * c.channels, c.channels, r0, n, s);
+    };
+    if (path == kDirect) return run_host_direct(c.src, alias, c.H, c.W, pix, (size_t)c.rs * esz, hull, band);
+    if (path == kBanded && stack_bands)
+      return run_host_banded(c.src, c.dst, c.H, c.W, pix, (size_t)c.rs * esz, hull, [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
+        dcp::StackArgs st;
+        memset(&st, 0, sizeof(st));
+        st.D = 1;
+        st.H = (int32_t)c.H;
+        st.W = (int32_t)c.W;
+        st.row_start = (double)r0;
+        st.nrows = (int32_t)n;
+        st.vol = (const float*)dsrc;
+        st.out = (float*)dband;
+        st.proj_stride = c.H * c.W;
+        st.row_stride = (int32_t)c.W;
+        st.proj_bytes = (uint32_t)((size_t)c.H * (size_t)c.W * 4);
+        return dcp::launch_stack(st, c.map, c.sampler, true, c.opts, s);
+      });
+    if (path == kBanded) return run_host_banded(c.src, c.dst, c.H, c.W, pix, (size_t)c.rs * esz, hull, band);
+  }
+  // staged whole: dense float32 rows packed on the way in, anything else as the extent it spans (the kernel's strided gather picks
+  // a column-strided view's elements: one channel of an interleaved image)
+  const bool pack = tuned_image && c.cs == 1;
+  HostTrip t;
+  t.src = c.src;
+  t.row_bytes = pack ? (size_t)c.W * esz : (size_t)((c.H - 1) * c.rs + (c.W - 1) * c.cs + c.channels) * esz;
+  t.rows = pack ? (size_t)c.H : 1;
+  t.pitch = pack ? (size_t)c.rs * esz : t.row_bytes;
+  if (c.kind == dcp::kCoords) {
+    t.y_up = c.ycoord;
+    t.x_up = c.xcoord;
+    t.plane = (size_t)c.npts * (c.coord_dtype == DCP_COORD_F64 ? 8 : 4);
+  }
+  t.dst = c.dst;
+  t.out_bytes = (size_t)(c.kind == dcp::kCoords ? c.npts : c.H * c.W * c.channels) * esz;
+  return host_round_trip(t, c.stream, [&](const void* dsrc, void* ddst, void* dy, void* dx) {
+    return launch_frame(c, dsrc, ddst, dy, dx, pack ? c.W : c.rs, pack ? 1 : c.cs, 0, 0, c.stream);
+  });
+}
+
+// the two dcp_map_points_* entry points: npts (y, x) pairs through a radial or perspective map, float64
+int map_points(dcp::MapKind kind, const double* yx_in, double* yx_out, int64_t npts, double xc, double yc, const double* fact, int nfact,
+               const double* coef, int mem_kind, int device, void* stream) {
+  int rc;
+  bool host = false;
+  if ((rc = mem_kind_of(mem_kind, &host)) != DCP_OK) return rc;
+  if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
+  if (npts > 0 && (!yx_in || !yx_out)) return fail(DCP_ERR_INVALID_ARG, "null point pointer");
+  dcp::MapArgs map;
+  if ((rc = frame_map(&map, kind, xc, yc, fact, nfact, coef, 0, 0)) != DCP_OK) return rc;
+  if (npts == 0) return DCP_OK;
   DeviceScope scope(device);
   if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
   hipStream_t st = (hipStream_t)stream;
-  dcp::TypedImageArgs a;
-  memset(&a, 0, sizeof(a));
-  a.H = (int32_t)H;
-  a.W = (int32_t)W;
-  a.src_stride = rs;
-  a.src_cstride = cs;
-  a.order = order;
-  a.dtype = dtype;
-  dcp::CoordArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.npts = npts;
-  ca.is_f64 = coord_dtype == DCP_COORD_F64;
-  ca.mode = mode;
-  const int64_t nout = map_kind == 3 ? npts : H * W;
-  // 8- / 16-bit integers, radial or perspective map, certified: the workgroup-box kernel (same arithmetic, LDS-staged)
-  dcp::MapArgs mapc = map;
-  auto staged_launch = [&](const void* dsrc_, void* ddst_, int64_t rs_, bool* taken) -> hipError_t {
-    *taken = false;
-    if ((map_kind != 0 && map_kind != 1) || cs != 1 || (double)extent_bytes_typed(H, W, rs_, 1, dtype) > 4294900000.0) return hipSuccess;
-    const dcp::MapKind kind = map_kind == 0 ? dcp::kRadial : dcp::kPersp;
-    mapc.tile_dev_ok = g_tile_cert.load() ? tile_deviation_certified(kind, mapc, H, W) : 0;
-    if (kind == dcp::kPersp) mapc.fast_div = homography_is_tame(mapc.coef, H, W);
-    dcp::ImageArgs im;
-    memset(&im, 0, sizeof(im));
-    im.H = (int32_t)H;
-    im.W = (int32_t)W;
-    im.src = (const float*)dsrc_;
-    im.dst = (float*)ddst_;
-    im.src_stride = (int32_t)rs_;
-    im.src_col_stride = 1;
-    im.src_bytes = (uint32_t)extent_bytes_typed(H, W, rs_, 1, dtype);
-    im.xcd_remap = current_opts().xcd_remap;
-    if (kind == dcp::kRadial && (dtype == dcp::kF64 || dtype == dcp::kI32 || dtype == dcp::kU32)) {
-      // 4- and 8-byte element types: the interleaved-pixel kernel with one channel (color_kernels.hip)
-      im.src_col_stride = 1;
-      return dcp::launch_color(im, mapc, 1, dtype, order == 0 ? dcp::kNearest : dcp::kScipy, current_opts(), st, taken);
-    }
-    return dcp::launch_wg_typed(kind, im, mapc, order, dtype, current_opts(), st, taken);
+  auto launch = [&](const void* in, void* out) {
+    return kind == dcp::kRadial ? dcp::launch_map_points((const double*)in, (double*)out, npts, map, st)
+                                : dcp::launch_map_points_persp((const double*)in, (double*)out, npts, map, st);
   };
-  if (mem_kind == DCP_MEM_DEVICE) {
-    bool taken = false;
-    DCP_HIP(staged_launch(src, dst, rs, &taken));
-    if (taken) return DCP_OK;
-    a.src = src;
-    a.dst = dst;
-    ca.ycoord = ycoord;
-    ca.xcoord = xcoord;
-    DCP_HIP(dcp::launch_typed_image(map_kind, a, map, ca, st));
+  if (!host) {
+    DCP_HIP(launch(yx_in, yx_out));
     return DCP_OK;
   }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *dsrc, *ddst, *dy = nullptr, *dx = nullptr;
-  const size_t ext = extent_bytes_typed(H, W, rs, cs, dtype), esz = (size_t)dcp::elem_size(dtype);
-  DCP_HIP(g_staging.get(0, ext, &dsrc));
-  DCP_HIP(g_staging.get(1, (size_t)nout * esz, &ddst));
-  DCP_HIP(hipMemcpyAsync(dsrc, src, ext, hipMemcpyHostToDevice, st));
-  if (map_kind == 3) {
-    const size_t csz = (size_t)npts * (ca.is_f64 ? 8 : 4);
-    DCP_HIP(g_staging.get(2, csz, &dy));
-    DCP_HIP(g_staging.get(3, csz, &dx));
-    DCP_HIP(hipMemcpyAsync(dy, ycoord, csz, hipMemcpyHostToDevice, st));
-    DCP_HIP(hipMemcpyAsync(dx, xcoord, csz, hipMemcpyHostToDevice, st));
-  }
-  a.src = dsrc;
-  a.dst = ddst;
-  ca.ycoord = dy;
-  ca.xcoord = dx;
-  bool taken = false;
-  DCP_HIP(staged_launch(dsrc, ddst, rs, &taken));
-  if (!taken) DCP_HIP(dcp::launch_typed_image(map_kind, a, map, ca, st));
-  DCP_HIP(hipMemcpyAsync(dst, ddst, (size_t)nout * esz, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  HostTrip t;
+  t.src = yx_in;
+  t.row_bytes = t.pitch = t.out_bytes = (size_t)npts * 16;
+  t.dst = yx_out;
+  return host_round_trip(t, st, [&](const void* din, void* dout, void*, void*) { return launch(din, dout); });
 }
 
 }  // namespace
 
 namespace dcpapi {
-bool host_direct_applies() { return host_direct_applies_here(); }
+bool host_direct_applies() { return host_path(kBandRows, kBandBytes, true, false, nullptr, nullptr) == kDirect; }
 }  // namespace dcpapi
 
 extern "C" {
@@ -590,21 +626,11 @@ int dcp_unwarp_image_f32(const float* src, float* dst, int64_t height, int64_t w
                          int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
                          int nfact, int order, int coord_round_f32, int blend_mode, int mem_kind, int device,
                          void* stream) {
-  int rc, sampler;
-  if ((rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, nullptr)) != DCP_OK) return rc;
-  if (beyond_32bit_offsets(height, width, src_row_stride, src_col_stride) && coord_round_f32)
-    return run_typed(0, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                     0, mem_kind, device, stream);
-  if ((rc = check_image(src, dst, height, width, src_row_stride, src_col_stride)) != DCP_OK) return rc;
-  {
-    int tall = 0;
-    map.tile_dev_ok = g_tile_cert.load() ? tile_deviation_certified(dcp::kRadial, map, height, width, &tall) : 0;
-    map.tall_ok = g_tile_cert.load() ? tall : 0;
-  }
-  return run_image(dcp::kRadial, src, dst, height, width, src_row_stride, src_col_stride, map, sampler,
-                   coord_round_f32 != 0, mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTuned, dcp::kRadial, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1,
+                                 xcenter, ycenter, list_fact, nfact, nullptr, Points{}, order, blend_mode, 0, coord_round_f32, mem_kind,
+                                 device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_unwarp_images_f32(const float* const* srcs, float* const* dsts, int nframes, int64_t height, int64_t width,
@@ -612,6 +638,8 @@ int dcp_unwarp_images_f32(const float* const* srcs, float* const* dsts, int nfra
                           const double* list_facts, int nfact, int order, int coord_round_f32, int blend_mode, int mem_kind,
                           int device, void* stream) {
   int rc, sampler;
+  bool host = false, unordered = false;     // (DCP_MEM_DEVICE_UNORDERED: frame by frame, every launch unordered)
+  if ((rc = mem_kind_of(mem_kind, &host, &unordered)) != DCP_OK) return rc;
   if (nframes < 0) return fail(DCP_ERR_INVALID_ARG, "nframes < 0");
   if (nframes == 0) return DCP_OK;
   if (!srcs || !dsts || !xcenters || !ycenters) return fail(DCP_ERR_INVALID_ARG, "null frame / centre array");
@@ -630,7 +658,7 @@ int dcp_unwarp_images_f32(const float* const* srcs, float* const* dsts, int nfra
   };
   // host frames are bound by PCIe: each goes through the single-frame host path (bands of rows, uploads and downloads
   // overlapped); float64 coordinates and sources beyond 32-bit offsets have no multi-frame kernel either
-  if (mem_kind != DCP_MEM_DEVICE || !coord_round_f32 || nframes == 1 || nfact > 10 ||
+  if (host || unordered || !coord_round_f32 || nframes == 1 || nfact > 10 ||
       beyond_32bit_offsets(height, width, src_row_stride, src_col_stride))
     return one_by_one(0);
   for (int i = 0; i < nframes; ++i)
@@ -680,38 +708,20 @@ int dcp_unwarp_images_f32(const float* const* srcs, float* const* dsts, int nfra
 int dcp_perspective_image_f32(const float* src, float* dst, int64_t height, int64_t width,
                               int64_t src_row_stride, int64_t src_col_stride, const double* list_coef,
                               int order, int blend_mode, int mem_kind, int device, void* stream) {
-  int rc, sampler;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  if ((rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, 0.0, 0.0, nullptr, 0, list_coef)) != DCP_OK) return rc;
-  if (height > 0 && width > 0) map.fast_div = homography_is_tame(list_coef, height, width);
-  if (beyond_32bit_offsets(height, width, src_row_stride, src_col_stride))
-    return run_typed(1, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                     0, mem_kind, device, stream);
-  if ((rc = check_image(src, dst, height, width, src_row_stride, src_col_stride)) != DCP_OK) return rc;
-  map.tile_dev_ok = g_tile_cert.load() ? tile_deviation_certified(dcp::kPersp, map, height, width) : 0;
-  return run_image(dcp::kPersp, src, dst, height, width, src_row_stride, src_col_stride, map, sampler, true,
-                   mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTuned, dcp::kPersp, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1, 0.0,
+                                 0.0, nullptr, 0, list_coef, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_unwarp_fused_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
                          int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
                          int nfact, const double* list_coef, int order, int blend_mode, int mem_kind,
                          int device, void* stream) {
-  int rc, sampler;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  if ((rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, list_coef)) != DCP_OK) return rc;
-  if (height > 0 && width > 0) map.fast_div = homography_is_tame(list_coef, height, width);
-  if (beyond_32bit_offsets(height, width, src_row_stride, src_col_stride))
-    return run_typed(2, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                     0, mem_kind, device, stream);
-  if ((rc = check_image(src, dst, height, width, src_row_stride, src_col_stride)) != DCP_OK) return rc;
-  map.tile_dev_ok = (g_tile_cert.load() && g_fused_wg.load()) ? tile_deviation_certified(dcp::kFused, map, height, width) : 0;
-  return run_image(dcp::kFused, src, dst, height, width, src_row_stride, src_col_stride, map, sampler, true,
-                   mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTuned, dcp::kFused, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1,
+                                 xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_remap_coords_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
@@ -724,112 +734,56 @@ int dcp_remap_coords_f32(const float* src, float* dst, int64_t height, int64_t w
 int dcp_remap_coords_mode_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
                               int64_t src_col_stride, const void* ycoord, const void* xcoord, int coord_dtype,
                               int64_t npts, int order, int boundary_mode, int blend_mode, int mem_kind, int device, void* stream) {
-  int rc, sampler;
-  if (boundary_mode < 0 || boundary_mode > 7) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", boundary_mode);
-  if (beyond_32bit_offsets(height, width, src_row_stride, src_col_stride)) {
-    dcp::MapArgs none;
-    memset(&none, 0, sizeof(none));
-    if ((rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
-    return run_typed(3, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, none, ycoord, xcoord, coord_dtype,
-                     npts, order, boundary_mode, mem_kind, device, stream);
-  }
-  if ((rc = check_image(src, dst, height, width, src_row_stride, src_col_stride)) != DCP_OK) return rc;
-  if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
-  if (npts > 0 && (!ycoord || !xcoord)) return fail(DCP_ERR_INVALID_ARG, "null coordinate pointer");
-  if (coord_dtype != DCP_COORD_F32 && coord_dtype != DCP_COORD_F64)
-    return fail(DCP_ERR_INVALID_ARG, "unknown coord_dtype %d", coord_dtype);
-  if (npts > 2147483647LL * 256) return fail(DCP_ERR_UNSUPPORTED, "too many points");
-  if ((rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
-  if (npts == 0) return DCP_OK;
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  dcp::ImageArgs img;
-  memset(&img, 0, sizeof(img));
-  img.H = (int32_t)height;
-  img.W = (int32_t)width;
-  img.src_stride = (int32_t)src_row_stride;
-  img.src_col_stride = (int32_t)src_col_stride;
-  img.src_bytes = extent_bytes(height, width, src_row_stride, src_col_stride);
-  dcp::CoordArgs ca;
-  ca.npts = npts;
-  ca.is_f64 = coord_dtype == DCP_COORD_F64;
-  ca.mode = boundary_mode;
-  hipStream_t st = (hipStream_t)stream;
-  if (mem_kind == DCP_MEM_DEVICE) {
-    img.src = src;
-    img.dst = dst;
-    ca.ycoord = ycoord;
-    ca.xcoord = xcoord;
-    DCP_HIP(dcp::launch_coords(img, ca, sampler, st));
-    return DCP_OK;
-  }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *dsrc, *ddst, *dy, *dx;
-  const size_t csz = (size_t)npts * (ca.is_f64 ? 8 : 4);
-  DCP_HIP(g_staging.get(0, img.src_bytes, &dsrc));
-  DCP_HIP(g_staging.get(1, (size_t)npts * 4, &ddst));
-  DCP_HIP(g_staging.get(2, csz, &dy));
-  DCP_HIP(g_staging.get(3, csz, &dx));
-  DCP_HIP(hipMemcpyAsync(dsrc, src, img.src_bytes, hipMemcpyHostToDevice, st));
-  DCP_HIP(hipMemcpyAsync(dy, ycoord, csz, hipMemcpyHostToDevice, st));
-  DCP_HIP(hipMemcpyAsync(dx, xcoord, csz, hipMemcpyHostToDevice, st));
-  img.src = (const float*)dsrc;
-  img.dst = (float*)ddst;
-  ca.ycoord = dy;
-  ca.xcoord = dx;
-  DCP_HIP(dcp::launch_coords(img, ca, sampler, st));
-  DCP_HIP(hipMemcpyAsync(dst, ddst, (size_t)npts * 4, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTuned, dcp::kCoords, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1, 0.0,
+                                 0.0, nullptr, 0, nullptr, Points{ycoord, xcoord, coord_dtype, npts}, order, blend_mode, boundary_mode, 1,
+                                 mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_unwarp_image_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
                            int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
                            int order, int boundary_mode, int mem_kind, int device, void* stream) {
-  int rc;
   // a large dense host frame, orders 0 / 1: the one-channel case of the interleaved entry point, whose host path moves
   // the frame in bands of rows with uploads and downloads overlapped (same arithmetic: scipy's exact blend)
-  if (mem_kind == DCP_MEM_HOST && order >= 0 && order <= 1 && boundary_mode >= 0 && boundary_mode <= 7 && src_col_stride == 1 && height >= 512 && dtype >= 0 &&
-      dtype < dcp::kNumElemTypes && (double)height * (double)width * (double)dcp::elem_size(dtype) >= 16.0 * 1048576.0)
+  if (mem_kind == DCP_MEM_HOST && order >= 0 && order <= 1 && boundary_mode >= 0 && boundary_mode <= 7 && src_col_stride == 1 && dtype >= 0 &&
+      dtype < dcp::kNumElemTypes && large_host_frame(height, (double)height * (double)width * (double)dcp::elem_size(dtype)))
     return dcp_unwarp_image_channels(src, dst, dtype, height, width, 1, src_row_stride, 1, xcenter, ycenter, list_fact, nfact,
                                      order, mem_kind, device, stream);
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, nullptr)) != DCP_OK) return rc;
-  return run_typed(0, src, dst, dtype, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                   boundary_mode, mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTyped, dcp::kRadial, src, dst, dtype, height, width, src_row_stride, src_col_stride, 1, xcenter,
+                                 ycenter, list_fact, nfact, nullptr, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device,
+                                 stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_perspective_image_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width,
                                 int64_t src_row_stride, int64_t src_col_stride, const double* list_coef, int order,
                                 int boundary_mode, int mem_kind, int device, void* stream) {
-  int rc;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, 0.0, 0.0, nullptr, 0, list_coef)) != DCP_OK) return rc;
-  if (height > 0 && width > 0) map.fast_div = homography_is_tame(list_coef, height, width);
-  return run_typed(1, src, dst, dtype, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                   boundary_mode, mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTyped, dcp::kPersp, src, dst, dtype, height, width, src_row_stride, src_col_stride, 1, 0.0, 0.0,
+                                 nullptr, 0, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_unwarp_fused_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
                            int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
                            const double* list_coef, int order, int boundary_mode, int mem_kind, int device, void* stream) {
-  int rc;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, list_coef)) != DCP_OK) return rc;
-  if (height > 0 && width > 0) map.fast_div = homography_is_tame(list_coef, height, width);
-  return run_typed(2, src, dst, dtype, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                   boundary_mode, mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTyped, dcp::kFused, src, dst, dtype, height, width, src_row_stride, src_col_stride, 1, xcenter,
+                                 ycenter, list_fact, nfact, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device,
+                                 stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_remap_coords_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
                            int64_t src_col_stride, const void* ycoord, const void* xcoord, int coord_dtype, int64_t npts,
                            int order, int boundary_mode, int mem_kind, int device, void* stream) {
-  dcp::MapArgs map;
-  memset(&map, 0, sizeof(map));
-  return run_typed(3, src, dst, dtype, height, width, src_row_stride, src_col_stride, map, ycoord, xcoord, coord_dtype,
-                   npts, order, boundary_mode, mem_kind, device, stream);
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecTyped, dcp::kCoords, src, dst, dtype, height, width, src_row_stride, src_col_stride, 1, 0.0, 0.0,
+                                 nullptr, 0, nullptr, Points{ycoord, xcoord, coord_dtype, npts}, order, DCP_BLEND_SCIPY, boundary_mode, 1,
+                                 mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_unwarp_image_channels(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels,
@@ -842,182 +796,94 @@ int dcp_unwarp_image_channels(const void* src, void* dst, int dtype, int64_t hei
 int dcp_unwarp_color_image(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
                            int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact, int order,
                            int blend_mode, int mem_kind, int device, void* stream) {
-  int rc;
-  if (channels < 1 || channels > 64) return fail(DCP_ERR_INVALID_ARG, "channels = %d outside [1, 64]", channels);
-  if (order < 0 || order > 1) return fail(DCP_ERR_UNSUPPORTED, "the interleaved-channel kernels take orders 0 and 1 (got %d)", order);
-  if (blend_mode != DCP_BLEND_SCIPY && blend_mode != DCP_BLEND_F64LERP)
-    return fail(DCP_ERR_UNSUPPORTED, "interleaved channels blend as scipy does (DCP_BLEND_SCIPY) or within one ulp of it (DCP_BLEND_F64LERP); got %d", blend_mode);
-  if (src_pixel_stride < channels) return fail(DCP_ERR_INVALID_ARG, "pixel stride %lld smaller than %d channels", (long long)src_pixel_stride, channels);
-  if ((rc = check_image_typed(src, dst, dtype, height, width, src_row_stride, src_pixel_stride)) != DCP_OK) return rc;
-  if (src_row_stride < (width - 1) * src_pixel_stride + channels && height > 1)
-    return fail(DCP_ERR_INVALID_ARG, "row stride %lld overlaps rows of %lld pixels", (long long)src_row_stride, (long long)width);
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, nullptr)) != DCP_OK) return rc;
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  hipStream_t st = (hipStream_t)stream;
-  // float32 only: the one-ulp factorisation; integer types always blend in scipy's exact order (their rounding ties depend on it)
-  const int sampler = order == 0 ? dcp::kNearest : (blend_mode == DCP_BLEND_F64LERP && dtype == dcp::kF32 ? dcp::kF64Lerp : dcp::kScipy);
-  dcp::TypedImageArgs a;
-  memset(&a, 0, sizeof(a));
-  a.H = (int32_t)height;
-  a.W = (int32_t)width;
-  a.src_stride = src_row_stride;
-  a.src_cstride = src_pixel_stride;
-  a.order = order;
-  a.dtype = dtype;
-  a.blend = sampler;
-  a.y0 = 0;
-  a.rows = (int32_t)height;
-  const size_t esz = (size_t)dcp::elem_size(dtype);
-  const dcp::LaunchOpts opts = current_opts();
-  map.tile_dev_ok = g_tile_cert.load() ? tile_deviation_certified(dcp::kRadial, map, height, width) : 0;
-  // rows [r0, r0 + n) of the result from the whole-frame source at dsrc: the workgroup-box kernel (remap_wg_color_kernel) where the
-  // call qualifies -- dense pixels of 3 / 4 channels, float32 / uint8 / uint16, certified map --, else one thread per pixel
-  auto launch_rows = [&](const void* dsrc, void* drows, int64_t rs_el, int64_t ps_el, int64_t r0, int64_t n, hipStream_t s) -> hipError_t {
-    const double ext = ((double)(height - 1) * (double)rs_el + (double)(width - 1) * (double)ps_el + (double)channels) * (double)esz;
-    if (ext <= 4294900000.0 && rs_el < (1ll << 31)) {
-      dcp::ImageArgs im;
-      memset(&im, 0, sizeof(im));
-      im.H = (int32_t)height;
-      im.W = (int32_t)width;
-      im.src = (const float*)dsrc;
-      im.dst = (float*)drows;
-      im.src_stride = (int32_t)rs_el;
-      im.src_col_stride = (int32_t)ps_el;
-      im.src_bytes = (uint32_t)ext;
-      im.y_origin = (int32_t)r0;
-      im.rows_out = (int32_t)n;
-      bool taken = false;
-      const hipError_t e = dcp::launch_color(im, map, channels, dtype, sampler, opts, s, &taken);
-      if (e != hipSuccess || taken) return e;
-    }
-    dcp::TypedImageArgs b = a;
-    b.src = dsrc;
-    b.dst = drows;
-    b.src_stride = rs_el;
-    b.src_cstride = ps_el;
-    b.y0 = (int32_t)r0;
-    b.rows = (int32_t)n;
-    return dcp::launch_typed_channels(b, map, channels, s);
-  };
-  if (mem_kind == DCP_MEM_DEVICE) {
-    DCP_HIP(launch_rows(src, dst, src_row_stride, src_pixel_stride, 0, height, st));
-    return DCP_OK;
-  }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  if (src_pixel_stride == channels && height >= 512 && (double)height * (double)width * (double)channels * (double)esz >= 16.0 * 1048576.0 &&
-      g_host_duplex.load() && (g_host_duplex.load() == 2 || runtime_overlaps_directions())) {
-    // dense interleaved frame: bands of rows, uploads and downloads overlapped (see run_host_banded)
-    return run_host_banded(src, dst, height, width, (size_t)channels * esz, (size_t)src_row_stride * esz,
-                                  [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) { host_row_band(map, height, width, (double)r0, n, b0, b1); },
-                                  [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
-                                    return launch_rows(dsrc, dband, width * channels, channels, r0, n, s);
-                                  });
-  }
-  const size_t ext = (size_t)((height - 1) * src_row_stride + (width - 1) * src_pixel_stride + channels) * esz;
-  const size_t obytes = (size_t)height * (size_t)width * (size_t)channels * esz;
-  void *dsrc, *ddst;
-  DCP_HIP(g_staging.get(0, ext, &dsrc));
-  DCP_HIP(g_staging.get(1, obytes, &ddst));
-  DCP_HIP(hipMemcpyAsync(dsrc, src, ext, hipMemcpyHostToDevice, st));
-  DCP_HIP(launch_rows(dsrc, ddst, src_row_stride, src_pixel_stride, 0, height, st));
-  DCP_HIP(hipMemcpyAsync(dst, ddst, obytes, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColour, dcp::kRadial, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
+                                 xcenter, ycenter, list_fact, nfact, nullptr, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_unwarp_image_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
+                                int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
+                                int nfact, int order, int boundary_mode, int mem_kind, int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecSpline, dcp::kRadial, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1,
+                                 xcenter, ycenter, list_fact, nfact, nullptr, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind,
+                                 device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_perspective_image_spline_f32(const float* src, float* dst, int64_t height, int64_t width,
+                                     int64_t src_row_stride, int64_t src_col_stride, const double* list_coef, int order,
+                                     int boundary_mode, int mem_kind, int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecSpline, dcp::kPersp, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1, 0.0,
+                                 0.0, nullptr, 0, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device, stream);
+  c.map.fast_div = 0;        // (this entry point has always divided the homography plainly; the typed one, at orders 2..5 too, does not)
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_unwarp_fused_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
+                                int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
+                                int nfact, const double* list_coef, int order, int boundary_mode, int mem_kind, int device,
+                                void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecSpline, dcp::kFused, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1,
+                                 xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind,
+                                 device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_remap_coords_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
+                                int64_t src_col_stride, const void* ycoord, const void* xcoord, int coord_dtype,
+                                int64_t npts, int order, int boundary_mode, int mem_kind, int device, void* stream) {
+  bool host = false;
+  if (npts == 0 && order >= 2 && order <= 5) return mem_kind_of(mem_kind, &host);     // (an empty call checks nothing else)
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecSpline, dcp::kCoords, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, 1, 0.0,
+                                 0.0, nullptr, 0, nullptr, Points{ycoord, xcoord, coord_dtype, npts}, order, DCP_BLEND_SCIPY, boundary_mode,
+                                 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
 }
 
 int dcp_map_points_f64(const double* yx_in, double* yx_out, int64_t npts, double xcenter, double ycenter,
                        const double* list_fact, int nfact, int mem_kind, int device, void* stream) {
-  int rc;
-  if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
-  if (npts > 0 && (!yx_in || !yx_out)) return fail(DCP_ERR_INVALID_ARG, "null point pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, nullptr)) != DCP_OK) return rc;
-  if (npts == 0) return DCP_OK;
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  hipStream_t st = (hipStream_t)stream;
-  if (mem_kind == DCP_MEM_DEVICE) {
-    DCP_HIP(dcp::launch_map_points(yx_in, yx_out, npts, map, st));
-    return DCP_OK;
-  }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *din, *dout;
-  const size_t bytes = (size_t)npts * 16;
-  DCP_HIP(g_staging.get(0, bytes, &din));
-  DCP_HIP(g_staging.get(1, bytes, &dout));
-  DCP_HIP(hipMemcpyAsync(din, yx_in, bytes, hipMemcpyHostToDevice, st));
-  DCP_HIP(dcp::launch_map_points((const double*)din, (double*)dout, npts, map, st));
-  DCP_HIP(hipMemcpyAsync(yx_out, dout, bytes, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  return map_points(dcp::kRadial, yx_in, yx_out, npts, xcenter, ycenter, list_fact, nfact, nullptr, mem_kind, device, stream);
 }
 
 int dcp_map_points_perspective_f64(const double* yx_in, double* yx_out, int64_t npts, const double* list_coef, int mem_kind, int device,
                                    void* stream) {
-  int rc;
-  if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
-  if (npts > 0 && (!yx_in || !yx_out)) return fail(DCP_ERR_INVALID_ARG, "null point pointer");
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, 0.0, 0.0, nullptr, 0, list_coef)) != DCP_OK) return rc;
-  if (npts == 0) return DCP_OK;
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  hipStream_t st = (hipStream_t)stream;
-  if (mem_kind == DCP_MEM_DEVICE) {
-    DCP_HIP(dcp::launch_map_points_persp(yx_in, yx_out, npts, map, st));
-    return DCP_OK;
-  }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *din, *dout;
-  const size_t bytes = (size_t)npts * 16;
-  DCP_HIP(g_staging.get(0, bytes, &din));
-  DCP_HIP(g_staging.get(1, bytes, &dout));
-  DCP_HIP(hipMemcpyAsync(din, yx_in, bytes, hipMemcpyHostToDevice, st));
-  DCP_HIP(dcp::launch_map_points_persp((const double*)din, (double*)dout, npts, map, st));
-  DCP_HIP(hipMemcpyAsync(yx_out, dout, bytes, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  return map_points(dcp::kPersp, yx_in, yx_out, npts, 0.0, 0.0, nullptr, 0, list_coef, mem_kind, device, stream);
 }
 
 int dcp_coordinate_map_f32(float* ymap, float* xmap, int64_t height, int64_t width, int map_kind, double xcenter,
                            double ycenter, const double* list_fact, int nfact, const double* list_coef, int mem_kind,
                            int device, void* stream) {
   int rc;
+  bool host = false;
+  if ((rc = mem_kind_of(mem_kind, &host)) != DCP_OK) return rc;
   if (!ymap || !xmap) return fail(DCP_ERR_INVALID_ARG, "null map pointer");
   if (height <= 0 || width <= 0 || height > 1073741823LL || width > 1073741823LL)
     return fail(DCP_ERR_INVALID_ARG, "map must be non-empty (got %lld x %lld)", (long long)height, (long long)width);
   if (map_kind < DCP_MAP_RADIAL || map_kind > DCP_MAP_FUSED) return fail(DCP_ERR_INVALID_ARG, "unknown map_kind %d", map_kind);
-  if (map_kind != DCP_MAP_RADIAL && !list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
+  const dcp::MapKind kind = (dcp::MapKind)map_kind;
   dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, map_kind == DCP_MAP_PERSPECTIVE ? nullptr : list_fact,
-                     map_kind == DCP_MAP_PERSPECTIVE ? 0 : nfact, map_kind == DCP_MAP_RADIAL ? nullptr : list_coef)) != DCP_OK)
-    return rc;
-  if (map_kind != DCP_MAP_RADIAL) map.fast_div = homography_is_tame(list_coef, height, width);
+  if ((rc = frame_map(&map, kind, xcenter, ycenter, list_fact, nfact, list_coef, height, width)) != DCP_OK) return rc;
   DeviceScope scope(device);
   if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
   dcp::ImageArgs img;
   memset(&img, 0, sizeof(img));
   img.H = (int32_t)height;
   img.W = (int32_t)width;
-  const dcp::MapKind kind = map_kind == DCP_MAP_RADIAL ? dcp::kRadial : map_kind == DCP_MAP_PERSPECTIVE ? dcp::kPersp : dcp::kFused;
   hipStream_t st = (hipStream_t)stream;
-  if (mem_kind == DCP_MEM_DEVICE) {
+  if (!host) {
     DCP_HIP(dcp::launch_coord_map(kind, img, map, ymap, xmap, st));
     return DCP_OK;
   }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *dy, *dx;
-  const size_t plane = (size_t)height * (size_t)width * 4;
-  DCP_HIP(g_staging.get(2, plane, &dy));
-  DCP_HIP(g_staging.get(3, plane, &dx));
-  DCP_HIP(dcp::launch_coord_map(kind, img, map, (float*)dy, (float*)dx, st));
-  DCP_HIP(hipMemcpyAsync(ymap, dy, plane, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipMemcpyAsync(xmap, dx, plane, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  HostTrip t;
+  t.y_down = ymap;
+  t.x_down = xmap;
+  t.plane = (size_t)height * (size_t)width * 4;
+  return host_round_trip(t, st, [&](const void*, void*, void* dy, void* dx) { return dcp::launch_coord_map(kind, img, map, (float*)dy, (float*)dx, st); });
 }
 
 }  // extern "C"

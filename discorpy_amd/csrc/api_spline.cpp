@@ -1,5 +1,5 @@
 // api_spline.cpp -- spline orders 2..5 (scipy's prefiltered B-spline interpolation, spline_kernels.hip): the
-// per-device coefficient workspace, host staging, and the *_spline_f32 entry points of the C ABI.
+// per-device coefficient workspace and the spline executor of FrameCall (api_image.cpp holds the entry points).
 #include "api_common.h"
 
 #include <cmath>
@@ -154,46 +154,24 @@ int release_spline_workspace() {
   return DCP_OK;
 }
 
-int run_spline(int map_kind, const void* src, void* dst, int dtype, int64_t H, int64_t W, int64_t rs, int64_t cs,
-               const dcp::MapArgs& map_in, const void* ycoord, const void* xcoord, int coord_dtype, int64_t npts, int order,
-               int mode, int mem_kind, int device, void* stream) {
-  int rc;
-  if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
-  dcp::MapArgs map = map_in;
-  // the host's tile-deviation certificate lets the gather stage its taps in LDS (spline_wg_kernel)
-  map.tile_dev_ok = (map_kind == 0 || map_kind == 1) && g_tile_cert.load() && H > 0 && W > 0
-                        ? tile_deviation_certified(map_kind == 0 ? dcp::kRadial : dcp::kPersp, map, H, W)
-                        : 0;
-  if (order < 2 || order > 5) return fail(DCP_ERR_INVALID_ARG, "spline order %d outside [2, 5]", order);
-  // bit 8 of boundary_mode (DCP_SPLINE_SCIPY_SUM): accumulate the taps in scipy's operation order instead of the factorised sum
-  const int exact_sum = (mode >= 0 && (mode & DCP_SPLINE_SCIPY_SUM)) ? 1 : 0;
-  if (mode >= 0) mode &= ~DCP_SPLINE_SCIPY_SUM;
-  if (mode < 0 || mode > 7) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
-  if (map_kind == 2) {
-    if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
-    if (npts > 0 && (!ycoord || !xcoord)) return fail(DCP_ERR_INVALID_ARG, "null coordinate pointer");
-    if (coord_dtype != DCP_COORD_F32 && coord_dtype != DCP_COORD_F64) return fail(DCP_ERR_INVALID_ARG, "unknown coord_dtype %d", coord_dtype);
-  }
-  if (H > 1000000 || W > 1000000) return fail(DCP_ERR_UNSUPPORTED, "image too large for the spline path");
-  DeviceScope scope(device);
-  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
-  hipStream_t st = (hipStream_t)stream;
+int run_spline(const FrameCall& c) {
+  hipStream_t st = c.stream;
   dcp::SplineArgs a;
   memset(&a, 0, sizeof(a));
-  a.H = (int32_t)H;
-  a.W = (int32_t)W;
-  a.src_dtype = a.dst_dtype = dtype;
-  a.order = order;
-  a.mode = mode;
-  a.exact_sum = exact_sum;
-  a.pad = (mode == dcp::kModeNearest || mode == dcp::kModeGridConstant) ? 12 : 0;
+  a.H = (int32_t)c.H;
+  a.W = (int32_t)c.W;
+  a.src_dtype = a.dst_dtype = c.dtype;
+  a.order = c.order;
+  a.mode = c.mode;
+  a.exact_sum = c.exact_sum;
+  a.pad = (c.mode == dcp::kModeNearest || c.mode == dcp::kModeGridConstant) ? 12 : 0;
   a.Hp = a.H + 2 * a.pad;
   a.Wp = a.W + 2 * a.pad;
   // ('nearest': scipy prefilters the edge-padded array with the reflect boundary -- see spline_filter_kind() in the oracle)
-  a.filter_kind = (mode == dcp::kModeReflect || mode == dcp::kModeGridMirror || mode == dcp::kModeNearest) ? dcp::kSplReflect
-                  : mode == dcp::kModeGridWrap                                 ? dcp::kSplWrap
-                                                                               : dcp::kSplMirror;
-  a.npoles = spline_poles(order, a.poles);
+  a.filter_kind = (c.mode == dcp::kModeReflect || c.mode == dcp::kModeGridMirror || c.mode == dcp::kModeNearest) ? dcp::kSplReflect
+                  : c.mode == dcp::kModeGridWrap                                       ? dcp::kSplWrap
+                                                                                       : dcp::kSplMirror;
+  a.npoles = spline_poles(c.order, a.poles);
   for (int axis = 0; axis < 2; ++axis) {
     const double n = axis == 0 ? (double)a.Hp : (double)a.Wp;
     for (int p = 0; p < a.npoles; ++p)
@@ -201,97 +179,42 @@ int run_spline(int map_kind, const void* src, void* dst, int dtype, int64_t H, i
   }
   const size_t plane = (size_t)a.Hp * (size_t)a.Wp * sizeof(double);
   int cur_dev = 0;
-  DCP_HIP(hipGetDevice(&cur_dev));                           // (DeviceScope above has selected it)
+  DCP_HIP(hipGetDevice(&cur_dev));                           // (run_frame has selected it)
   if (cur_dev < 0 || cur_dev >= 64) return fail(DCP_ERR_UNSUPPORTED, "device index %d", cur_dev);
   SplineWorkspace::Slot* slot = nullptr;
   DCP_HIP(g_spline_ws.acquire(2 * plane, st, cur_dev, &slot));
   SlotGuard guard{slot, st};
   a.coef = (double*)slot->buf;
   a.scratch = a.coef + (size_t)a.Hp * (size_t)a.Wp;
+  a.src_stride = (int32_t)c.rs;
+  a.src_cstride = (int32_t)c.cs;
   dcp::CoordArgs ca;
   memset(&ca, 0, sizeof(ca));
-  ca.npts = npts;
-  ca.is_f64 = coord_dtype == DCP_COORD_F64;
-  const int64_t nout = map_kind == 2 ? npts : H * W;
-  if (mem_kind == DCP_MEM_DEVICE) {
-    a.src = src;
-    a.src_stride = (int32_t)rs;
-    a.src_cstride = (int32_t)cs;
-    ca.ycoord = ycoord;
-    ca.xcoord = xcoord;
-    DCP_HIP(dcp::launch_spline(a, map_kind, map, ca, dst, st));
+  ca.npts = c.npts;
+  ca.is_f64 = c.coord_dtype == DCP_COORD_F64;
+  if (!c.host) {
+    a.src = c.src;
+    ca.ycoord = c.ycoord;
+    ca.xcoord = c.xcoord;
+    DCP_HIP(dcp::launch_spline(a, c.kind, c.map, ca, c.dst, st));
     return DCP_OK;
   }
-  if (mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", mem_kind);
-  void *dsrc, *ddst, *dy = nullptr, *dx = nullptr;
-  const size_t ext = extent_bytes_typed(H, W, rs, cs, dtype), esz = (size_t)dcp::elem_size(dtype);
-  DCP_HIP(g_staging.get(0, ext, &dsrc));
-  DCP_HIP(g_staging.get(1, (size_t)(nout > 0 ? nout : 1) * esz, &ddst));
-  DCP_HIP(hipMemcpyAsync(dsrc, src, ext, hipMemcpyHostToDevice, st));
-  if (map_kind == 2 && npts > 0) {
-    const size_t csz = (size_t)npts * (ca.is_f64 ? 8 : 4);
-    DCP_HIP(g_staging.get(2, csz, &dy));
-    DCP_HIP(g_staging.get(3, csz, &dx));
-    DCP_HIP(hipMemcpyAsync(dy, ycoord, csz, hipMemcpyHostToDevice, st));
-    DCP_HIP(hipMemcpyAsync(dx, xcoord, csz, hipMemcpyHostToDevice, st));
+  HostTrip t;
+  t.src = c.src;
+  t.row_bytes = t.pitch = extent_bytes_typed(c.H, c.W, c.rs, c.cs, c.dtype);
+  if (c.kind == dcp::kCoords) {
+    t.y_up = c.ycoord;
+    t.x_up = c.xcoord;
+    t.plane = (size_t)c.npts * (ca.is_f64 ? 8 : 4);
   }
-  a.src = dsrc;
-  a.src_stride = (int32_t)rs;
-  a.src_cstride = (int32_t)cs;
-  ca.ycoord = dy;
-  ca.xcoord = dx;
-  DCP_HIP(dcp::launch_spline(a, map_kind, map, ca, ddst, st));
-  if (nout > 0) DCP_HIP(hipMemcpyAsync(dst, ddst, (size_t)nout * esz, hipMemcpyDeviceToHost, st));
-  DCP_HIP(hipStreamSynchronize(st));
-  return DCP_OK;
+  t.dst = c.dst;
+  t.out_bytes = (size_t)(c.kind == dcp::kCoords ? c.npts : c.H * c.W) * (size_t)dcp::elem_size(c.dtype);
+  return host_round_trip(t, st, [&](const void* dsrc, void* ddst, void* dy, void* dx) {
+    a.src = dsrc;
+    ca.ycoord = dy;
+    ca.xcoord = dx;
+    return dcp::launch_spline(a, c.kind, c.map, ca, ddst, st);
+  });
 }
 
 }  // namespace dcpapi
-
-extern "C" {
-
-int dcp_unwarp_image_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
-                                int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
-                                int nfact, int order, int boundary_mode, int mem_kind, int device, void* stream) {
-  int rc;
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, nullptr)) != DCP_OK) return rc;
-  return run_spline(0, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                    boundary_mode, mem_kind, device, stream);
-}
-
-int dcp_perspective_image_spline_f32(const float* src, float* dst, int64_t height, int64_t width,
-                                     int64_t src_row_stride, int64_t src_col_stride, const double* list_coef, int order,
-                                     int boundary_mode, int mem_kind, int device, void* stream) {
-  int rc;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, 0.0, 0.0, nullptr, 0, list_coef)) != DCP_OK) return rc;
-  return run_spline(1, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0, order,
-                    boundary_mode, mem_kind, device, stream);
-}
-
-int dcp_unwarp_fused_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
-                                int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
-                                int nfact, const double* list_coef, int order, int boundary_mode, int mem_kind, int device,
-                                void* stream) {
-  int rc;
-  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
-  dcp::MapArgs map;
-  if ((rc = fill_map(&map, xcenter, ycenter, list_fact, nfact, list_coef)) != DCP_OK) return rc;
-  if (height > 0 && width > 0) map.fast_div = homography_is_tame(list_coef, height, width);
-  return run_spline(3, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, nullptr, nullptr, 0, 0,
-                    order, boundary_mode, mem_kind, device, stream);
-}
-
-int dcp_remap_coords_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
-                                int64_t src_col_stride, const void* ycoord, const void* xcoord, int coord_dtype,
-                                int64_t npts, int order, int boundary_mode, int mem_kind, int device, void* stream) {
-  dcp::MapArgs map;
-  memset(&map, 0, sizeof(map));
-  if (npts == 0) return (order < 2 || order > 5) ? fail(DCP_ERR_INVALID_ARG, "spline order %d outside [2, 5]", order) : DCP_OK;
-  return run_spline(2, src, dst, dcp::kF32, height, width, src_row_stride, src_col_stride, map, ycoord, xcoord, coord_dtype, npts,
-                    order, boundary_mode, mem_kind, device, stream);
-}
-
-}  // extern "C"

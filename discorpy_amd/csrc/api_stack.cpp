@@ -141,12 +141,13 @@ int run_stack(const StackCall& c) {
   if ((depth + opts.d_chunk - 1) / opts.d_chunk > 65535) opts.d_chunk = (int)((depth + 65534) / 65535);
   const size_t esz = (size_t)dcp::elem_size(c.dtype), osz = c.out_f32 ? 4 : esz;
   hipStream_t hs = (hipStream_t)c.stream;
-  if (c.mem_kind == DCP_MEM_DEVICE) {
+  bool host = false;
+  if (const int rc = mem_kind_of(c.mem_kind, &host)) return rc;
+  if (!host) {
     const char* base = (const char*)c.vol - (size_t)(c.band_start * c.row_stride) * esz;
     DCP_HIP(launch_stack_any(c, fast, base, c.out, depth, c.proj_stride, c.row_stride, c.band_start + c.band_rows, opts, hs));
     return DCP_OK;
   }
-  if (c.mem_kind != DCP_MEM_HOST) return fail(DCP_ERR_INVALID_ARG, "unknown mem_kind %d", c.mem_kind);
   // Host stack.  Only the reachable row band is shipped, and projections are independent
   // (postprocessing.py:226-228, 310-312), so the stack streams through the GPU in depth chunks: while
   // chunk k is copied back by a second host thread, chunk k+1 is uploaded and computed (PCIe is full

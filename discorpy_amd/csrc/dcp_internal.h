@@ -14,8 +14,9 @@ constexpr int kMaxTileRows = 64;   // rows one workgroup walks (runtime option t
 // sampler selector: order 0, or order 1 with one of the three blend arithmetics
 enum Sampler : int { kNearest = 0, kScipy = 1, kF64Lerp = 2, kF32Lerp = 3 };
 
-// what maps an output pixel to a source coordinate
-enum MapKind : int { kRadial = 0, kPersp = 1, kFused = 2 };
+// what maps an output pixel to a source coordinate (kCoords: explicit coordinates, one output value per point)
+// (DCP_MAP_RADIAL / _PERSPECTIVE / _FUSED of include/discorpy_hip.h are the first three)
+enum MapKind : int { kRadial = 0, kPersp = 1, kFused = 2, kCoords = 3 };
 
 struct ImageArgs {
   const float* src;
@@ -192,7 +193,6 @@ hipError_t read_bounds_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
-// spline_kernels.hip: map_kind 0 radial, 1 perspective, 2 explicit coordinates
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
 void set_box_table(int v);      // option "box_table": remap_wg_kernel reads its tile hulls from box_table_kernel's table (0 never, 1 where it pays)
 int get_box_table();
@@ -207,10 +207,11 @@ void set_pf2d_two_pole(int v);  // 0: the two-pole spline orders (4, 5) on splin
 int get_pf2d_two_pole();
 void set_spline_xcd(int v);     // 0: spline_wg_kernel's tiles in plain launch order (option "spline_xcd")
 int get_spline_xcd();
-hipError_t launch_spline(const SplineArgs& a, int map_kind, const MapArgs& map, const CoordArgs& ca, void* dst,
+// spline_kernels.hip: any MapKind (kCoords: ca.npts points into dst)
+hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, const CoordArgs& ca, void* dst,
                          hipStream_t stream);
-// typed_kernels.hip: map_kind 0 radial, 1 perspective, 2 fused, 3 explicit coordinates
-hipError_t launch_typed_image(int map_kind, const TypedImageArgs& img, const MapArgs& map, const CoordArgs& ca,
+// typed_kernels.hip: any MapKind (kCoords: ca.npts points into img.dst)
+hipError_t launch_typed_image(MapKind kind, const TypedImageArgs& img, const MapArgs& map, const CoordArgs& ca,
                               hipStream_t stream);
 hipError_t launch_typed_stack(const TypedStackArgs& st, const MapArgs& map, hipStream_t stream);
 // n points (y, x) -> centre + B(r) (p - centre), float64

@@ -1746,7 +1746,7 @@ static hipError_t launch_remap_order(const SplineArgs& a, const MapArgs& map, co
 
 DCP_DEFINE_BOUNDS_READER(read_bounds_spline)
 
-hipError_t launch_spline(const SplineArgs& a, int map_kind, const MapArgs& map, const CoordArgs& ca, void* dst,
+hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, const CoordArgs& ca, void* dst,
                          hipStream_t stream) {
   // prefilter: axis 0 on the (Hp x Wp) plane, transpose, axis 1 as axis 0 of the (Wp x Hp) plane,
   // transpose back.  Two planes ping-pong: a.coef (A) and a.scratch (B); the result ends in A.
@@ -1999,10 +1999,10 @@ hipError_t launch_spline(const SplineArgs& a, int map_kind, const MapArgs& map, 
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t total = map_kind == 2 ? ca.npts : (int64_t)a.H * a.W;
+  const int64_t total = kind == kCoords ? ca.npts : (int64_t)a.H * a.W;
   if (total == 0) return hipSuccess;
   // certified radial / perspective maps on frames of at least one workgroup tile: the taps out of LDS
-  const bool wg = (map_kind == 0 || map_kind == 1) && map.tile_dev_ok >= 2 && g_spline_wg && a.H >= kSwTH && a.W >= kSwTW &&
+  const bool wg = (kind == kRadial || kind == kPersp) && map.tile_dev_ok >= 2 && g_spline_wg && a.H >= kSwTH && a.W >= kSwTW &&
                   (int64_t)a.Hp * a.Wp * 8 < ((int64_t)1 << 32) && a.Hp < 65535 * kSwTH;
   {
     char name[160];
@@ -2015,13 +2015,16 @@ hipError_t launch_spline(const SplineArgs& a, int map_kind, const MapArgs& map, 
     set_last_kernel_name(name);
   }
   if (wg) {
-    if (map_kind == 0) return launch_spline_wg<kRadial>(a, map, dst, stream);
+    if (kind == kRadial) return launch_spline_wg<kRadial>(a, map, dst, stream);
     return launch_spline_wg<kPersp>(a, map, dst, stream);
   }
-  if (map_kind == 0) return launch_remap_order<0>(a, map, ca, dst, total, stream);
-  if (map_kind == 1) return launch_remap_order<1>(a, map, ca, dst, total, stream);
-  if (map_kind == 3) return launch_remap_order<3>(a, map, ca, dst, total, stream);
-  return launch_remap_order<2>(a, map, ca, dst, total, stream);
+  // spline_remap_kernel's MAPKIND: 0 radial, 1 perspective, 2 explicit coordinates, 3 fused
+  switch (kind) {
+    case kRadial: return launch_remap_order<0>(a, map, ca, dst, total, stream);
+    case kPersp: return launch_remap_order<1>(a, map, ca, dst, total, stream);
+    case kFused: return launch_remap_order<3>(a, map, ca, dst, total, stream);
+    default: return launch_remap_order<2>(a, map, ca, dst, total, stream);
+  }
 }
 
 }  // namespace dcp

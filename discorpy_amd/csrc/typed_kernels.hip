@@ -251,17 +251,17 @@ static dim3 image_grid(int H, int W) {
 }
 
 template <typename T>
-static hipError_t launch_image_t(int map_kind, const TypedImageArgs& a, const MapArgs& map, const CoordArgs& ca,
+static hipError_t launch_image_t(MapKind kind, const TypedImageArgs& a, const MapArgs& map, const CoordArgs& ca,
                                  hipStream_t stream) {
-  const int64_t total = map_kind == 3 ? ca.npts : (int64_t)a.H * a.W;
+  const int64_t total = kind == kCoords ? ca.npts : (int64_t)a.H * a.W;
   if (total == 0) return hipSuccess;
   const dim3 block(kTypedBlock);
-  const dim3 grid = map_kind == 3 ? dim3((unsigned)((total + kTypedBlock - 1) / kTypedBlock)) : image_grid(a.H, a.W);
-  switch (map_kind) {
-    case 0: hipLaunchKernelGGL((typed_image_kernel<T, kRadial>), grid, block, 0, stream, a, map, ca); break;
-    case 1: hipLaunchKernelGGL((typed_image_kernel<T, kPersp>), grid, block, 0, stream, a, map, ca); break;
-    case 2: hipLaunchKernelGGL((typed_image_kernel<T, kFused>), grid, block, 0, stream, a, map, ca); break;
-    default: hipLaunchKernelGGL((typed_image_kernel<T, 3>), grid, block, 0, stream, a, map, ca); break;
+  const dim3 grid = kind == kCoords ? dim3((unsigned)((total + kTypedBlock - 1) / kTypedBlock)) : image_grid(a.H, a.W);
+  switch (kind) {
+    case kRadial: hipLaunchKernelGGL((typed_image_kernel<T, kRadial>), grid, block, 0, stream, a, map, ca); break;
+    case kPersp: hipLaunchKernelGGL((typed_image_kernel<T, kPersp>), grid, block, 0, stream, a, map, ca); break;
+    case kFused: hipLaunchKernelGGL((typed_image_kernel<T, kFused>), grid, block, 0, stream, a, map, ca); break;
+    default: hipLaunchKernelGGL((typed_image_kernel<T, kCoords>), grid, block, 0, stream, a, map, ca); break;
   }
   return hipGetLastError();
 }
@@ -282,10 +282,10 @@ static hipError_t launch_image_t(int map_kind, const TypedImageArgs& a, const Ma
     default: return hipErrorInvalidValue;           \
   }
 
-hipError_t launch_typed_image(int map_kind, const TypedImageArgs& a, const MapArgs& map, const CoordArgs& ca,
+hipError_t launch_typed_image(MapKind kind, const TypedImageArgs& a, const MapArgs& map, const CoordArgs& ca,
                               hipStream_t stream) {
   set_last_kernel_name("typed_image_kernel (one thread per pixel, any element type)");
-#define DCP_CALL(T) launch_image_t<T>(map_kind, a, map, ca, stream)
+#define DCP_CALL(T) launch_image_t<T>(kind, a, map, ca, stream)
   DCP_TYPED_DISPATCH(a.dtype, DCP_CALL)
 #undef DCP_CALL
 }

@@ -50,7 +50,8 @@ extern "C" {
  * the ramp of the next, which is what dcp_unwarp_images_f32 gets from one launch (profiles/r06a_dispatch_modes.txt).  The caller
  * vouches that the call reads nothing an unfinished earlier call on the stream writes and writes nothing it reads or writes;
  * events, copies and synchronisations on the stream still wait for every earlier launch.  Accepted by dcp_unwarp_image_f32,
- * dcp_perspective_image_f32 and dcp_unwarp_fused_f32 (orders 0 / 1); DCP_ERR_INVALID_ARG elsewhere. */
+ * dcp_perspective_image_f32 and dcp_unwarp_fused_f32 (orders 0 / 1), and by dcp_unwarp_images_f32, whose frames then go one by
+ * one, each unordered; DCP_ERR_INVALID_ARG elsewhere. */
 #define DCP_MEM_DEVICE_UNORDERED 0x101
 
 #define DCP_BLEND_SCIPY 0

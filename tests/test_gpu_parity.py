@@ -1252,6 +1252,19 @@ def test_frame_larger_than_4_gib(hip, orc):
     for r0 in (3, 20000, H - 2):
         b0, bn = hip.stack_row_band(H, W, *a, r0, 1)
         assert np.isin(out0[r0], img[b0:b0 + bn]).all(), r0
+    del out0
+    # the same frame in device memory: DCP_MEM_DEVICE_UNORDERED goes to the generic kernels as well, as an ordered launch
+    L = hip.lib()
+    src = hip.DeviceBuffer(img.nbytes).upload(img)
+    fa, nf = hip.fact_array(a[2])
+    got = []
+    for mem in (hip.MEM_DEVICE, hip.MEM_DEVICE_UNORDERED):
+        d = hip.DeviceBuffer(img.nbytes)
+        hip.check(L.dcp_unwarp_image_f32(src.ptr, d.ptr, H, W, W, 1, a[0], a[1], fa, nf, 1, 1, hip.BLEND_SCIPY, mem, -1, None))
+        got.append(d.download((H, W), np.float32))
+        d.free()
+    src.free()
+    assert np.array_equal(got[0], got[1])
 
 
 def test_randomised_differential_campaign(hip, orc):
