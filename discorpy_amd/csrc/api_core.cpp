@@ -613,6 +613,9 @@ int dcp_set_option(const char* key_in, int value) {
   } else if (!strcmp(key, "box_table")) {
     if (value < 0 || value > 2) return fail(DCP_ERR_INVALID_ARG, "box_table must be 0, 1 or 2");
     dcp::set_box_table(value);        // 0: every wave of remap_wg_kernel evaluates its tile's corners; 1: once per tile by box_table_kernel where it pays
+  } else if (!strcmp(key, "frame_plan")) {
+    if (value < 0 || value > 2) return fail(DCP_ERR_INVALID_ARG, "frame_plan must be 0, 1 or 2");
+    dcp::set_frame_plan(value);       // 0: remap_wg_kernel never runs on a frame plan (A/B); 1: a calibration's plan is built when it is seen the second time; 2: the first
   } else if (!strcmp(key, "spline_wg")) {
     dcp::set_spline_wg(value ? 1 : 0);
   } else if (!strcmp(key, "spline_tiled")) {
@@ -661,6 +664,14 @@ int dcp_get_option(const char* key_in, int* value) {
   else if (!strcmp(key, "spline_xcd")) *value = dcp::get_spline_xcd();
   else if (!strcmp(key, "spline_wg")) *value = dcp::get_spline_wg();
   else if (!strcmp(key, "box_table")) *value = dcp::get_box_table();
+  else if (!strcmp(key, "frame_plan")) *value = dcp::get_frame_plan();
+  else if (!strcmp(key, "frame_plan_tiles") || !strcmp(key, "frame_plan_exact_tiles")) {
+    // read-only: the 64 x 16 wave tiles of the plan built last on the current device, and how many of them keep the exact evaluation
+    // (read back from the device here, outside any frame call; 0 / 0: no plan yet)
+    int tiles = 0, exact = 0;
+    DCP_HIP(dcp::frame_plan_last_counts(&tiles, &exact));
+    *value = !strcmp(key, "frame_plan_tiles") ? tiles : exact;
+  }
   else if (!strcmp(key, "stack_wg")) *value = g_stack_wg;
   else if (!strcmp(key, "int_exact")) *value = g_int_exact;
   else if (!strcmp(key, "host_direct")) *value = g_host_direct;
@@ -689,7 +700,9 @@ int dcp_release_scratch(void) {
   // the calling thread's staging buffers and streams (DCP_MEM_HOST calls), and the spline planes of every device
   g_staging.release();
   g_host_streams.release();
-  return release_spline_workspace();
+  const int rc = release_spline_workspace();
+  dcp::frame_plan_release();          // (synchronises every device that holds plans first)
+  return rc;
 }
 
 int dcp_debug_counters(uint64_t* out, int n, int reset) {

@@ -334,6 +334,53 @@ __device__ __forceinline__ void map_coord(const MapArgs& map, const double (*s_r
   *yd_out = yd;
 }
 
+// ------------------------------------------------------------------ the radial factor down a column, interpolated (frame plans)
+
+// The sixteen float32 coordinate pairs of one column of a 64 x 16 wave tile under the radial map, unclipped, with the radial factor f
+// evaluated exactly (map_coord's chain: sqrt_pos, even / odd Horner) on rows 0, 5, 10, 15 only and taken from the cubic through
+// those four values on the other twelve rows: Newton form on the nodes, f_k = f0 + k (d1 + (k - 5) (d2 + (k - 10) d3)), 3 fused
+// multiply-adds per row in place of 11 float64 operations and a v_rsq_f64.  Down a column f is smooth enough that on almost every
+// tile all 2 048 float32 values equal those of map_coord; WHICH tiles is decided on the device by plan_table_kernel, which calls
+// this very function and compares -- so the frame kernel calls it too, and nothing here may be written so that the compiler could
+// evaluate it differently in two callers: differences and products only, every multiply-add an explicit __builtin_fma
+// (-ffp-contract=off; a - b and a * b alone have one rounding whatever surrounds them).
+// `between(integral_constant<int, j>)`, j = 0..5, is called in front of the four node rows and the first two interpolated rows: the
+// frame kernel issues the six loads of its fill there; it takes no part in the arithmetic.
+template <int NF, typename Between>
+__device__ __forceinline__ void radial_rows_interp(const MapArgs& map, const double (*s_row)[2], const ColCtx& c, float* xf, float* yf,
+                                                   Between&& between) {
+  static_assert(NF >= 0, "unrolled polynomial only");
+  double f[4];
+  auto node = [&](auto nc) {
+    constexpr int n = decltype(nc)::value, k = 5 * n;
+    between(std::integral_constant<int, n>{});
+    const double r2 = c.cx1 + s_row[k][1];
+    const double g = sqrt_pos(r2);                 // r2 > 0 (row table)
+    f[n] = poly_inline<NF>(map.fact, c.lead_e, c.lead_o, r2, g);
+    xf[k] = (float)__builtin_fma(f[n], c.cx0, map.xc);
+    yf[k] = (float)__builtin_fma(f[n], s_row[k][0], map.yc);
+  };
+  node(std::integral_constant<int, 0>{});
+  node(std::integral_constant<int, 1>{});
+  node(std::integral_constant<int, 2>{});
+  node(std::integral_constant<int, 3>{});
+  // divided differences on the nodes 0, 5, 10, 15: first / 5, second / (2 * 25), third / (6 * 125)
+  const double e1 = f[1] - f[0], e2 = f[2] - f[1], e3 = f[3] - f[2];
+  const double s2 = e2 - e1, t2 = e3 - e2;
+  const double s3 = t2 - s2;
+  const double d1 = e1 * 0.2, d2 = s2 * 0.02, d3 = s3 * (1.0 / 750.0);
+  const double f0 = f[0];
+#pragma unroll
+  for (int k = 1; k < 15; ++k) {
+    if (k % 5 == 0) continue;
+    if (k == 1) between(std::integral_constant<int, 4>{});
+    if (k == 2) between(std::integral_constant<int, 5>{});
+    const double fk = __builtin_fma((double)k, __builtin_fma((double)(k - 5), __builtin_fma((double)(k - 10), d3, d2), d1), f0);
+    xf[k] = (float)__builtin_fma(fk, c.cx0, map.xc);
+    yf[k] = (float)__builtin_fma(fk, s_row[k][0], map.yc);
+  }
+}
+
 // One pixel of the radial or perspective map without hoisting, polynomial length fixed at compile time (NF >= 0: coefficients
 // straight from the kernel arguments) -- the corner pixels of a workgroup tile (remap_wg_kernel, spline_wg_kernel).
 template <int KIND, int NF>

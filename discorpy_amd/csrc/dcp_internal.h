@@ -37,6 +37,8 @@ struct ImageArgs {
   int32_t int_exact;       // integer element types: 1 = tiles at coordinates >= 32 take the exact factorised blend (exact_lerp_pairs)
   const int32_t* boxes = nullptr;   // remap_wg_kernel: corner hulls (x0, x1, y0, y1) of every 128 x 32 tile, frame-major, from box_table_kernel
                                     // (nullptr: every wave evaluates its workgroup's corners itself)
+                                    // remap_wg_kernel<.., PLAN>: a frame plan (frame_plan.cpp) -- the hulls of the tiles_x * tiles_y tiles, then one
+                                    // word per tile, bit w set = wave tile w of the tile may take its coordinate rows from radial_rows_interp
 };
 
 struct MapArgs {
@@ -194,6 +196,17 @@ hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
+// Frame plans (frame_plan.cpp): per calibration and frame shape, the hull of every 128 x 32 tile and a certificate bit per 64 x 16 wave
+// tile, built once on the device by plan_table_kernel and kept for the frames that follow.  Layout of a plan of n tiles, in int32 words:
+// [0, 4n) hulls (x0, x1, y0, y1) as box_table_kernel writes them, [4n, 5n) certificate words (bit w = wave tile w of the tile).
+typedef hipError_t (*PlanBuildFn)(const ImageArgs& img, const MapArgs& map, int32_t* plan, hipStream_t stream);
+// The plan for this launch (img: H, W, y_origin, rows_out, tiles_x, tiles_y of remap_wg_kernel; the current device), or nullptr: the
+// launch goes without one.  *ordered = true: the plan may still be under construction on the device -- the launch that reads it must keep its barrier bit.
+const int32_t* frame_plan_lookup(const ImageArgs& img, const MapArgs& map, hipStream_t stream, PlanBuildFn build, bool* ordered);
+void set_frame_plan(int v);     // option "frame_plan": 0 never, 1 build on the second sighting of a calibration, 2 on the first
+int get_frame_plan();
+hipError_t frame_plan_last_counts(int* wave_tiles, int* exact_tiles);    // of the plan built last (waits for its build; not on a frame's path)
+void frame_plan_release();      // frees every plan of every device (each device that holds plans is synchronised first)
 void set_box_table(int v);      // option "box_table": remap_wg_kernel reads its tile hulls from box_table_kernel's table (0 never, 1 where it pays)
 int get_box_table();
 int get_spline_wg();

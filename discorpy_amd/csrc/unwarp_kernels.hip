@@ -726,9 +726,12 @@ __device__ __forceinline__ void wg_corner_tap(const ImageArgs& img, const MapArg
 // integer result depends on it at rounding ties) and convert as scipy does: round half away from zero, saturate.
 // ImageArgs::src / dst / src_stride / src_bytes keep their meaning (pointers reinterpreted, stride in ELEMENTS, extent in bytes).
 // (the body is a device function: the single-frame kernel and the multi-frame kernel remap_wg_batch_kernel share it)
-template <int KIND, int NF, int SAMPLER, typename T>
+// PLAN: the launch carries a frame plan (frame_plan.cpp; float32, radial map, NF >= 0): every tile's hull comes from the plan's table, and
+// a wave tile whose certificate bit is set takes its twelve non-node coordinate rows from the cubic of radial_rows_interp.
+template <int KIND, int NF, int SAMPLER, typename T, bool PLAN = false>
 __device__ __forceinline__ void remap_wg_body(const ImageArgs& img, const MapArgs& map) {
   constexpr bool kIsF32 = std::is_same<T, float>::value;
+  static_assert(!PLAN || (kIsF32 && KIND == kRadial && NF >= 0), "frame plans: float32, radial map, unrolled polynomial");
   constexpr int ES = (int)sizeof(T);                           // element size in bytes
   constexpr int CH = ES == 4 ? 36 : (ES == 2 ? 20 : 10);       // 16-byte chunks per slab row
   constexpr int PB = CH * 16;                                  // slab pitch in bytes
@@ -775,7 +778,8 @@ __device__ __forceinline__ void remap_wg_body(const ImageArgs& img, const MapArg
   // last valid ones, so the corners span exactly the valid part of the tile.  The values may differ from the
   // row-hoisted evaluation of phase 1 in the last bits; the certificate leaves 0.05 px for that.
   int cx0, cx1, cy0, cy1;
-  if (img.boxes != nullptr) {
+  [[maybe_unused]] bool certified = false;       // PLAN: plan_table_kernel found the interpolated rows of this wave tile equal to the exact ones
+  if (PLAN || img.boxes != nullptr) {
     // (the hull was computed once per tile by box_table_kernel with the same code: four scalars from one scalar load,
     // instead of ~70 vector instructions in each of the four waves)
     typedef __attribute__((address_space(4))) const int32_t* const_ptr;
@@ -784,6 +788,11 @@ __device__ __forceinline__ void remap_wg_body(const ImageArgs& img, const MapArg
     cx1 = b[1];
     cy0 = b[2];
     cy1 = b[3];
+    if constexpr (PLAN) {
+      // (the certificate words follow the hulls of the plan's tiles_x * tiles_y tiles)
+      const const_ptr c = (const_ptr)(img.boxes + (4 * (size_t)img.tiles_y * img.tiles_x + (size_t)ty * img.tiles_x + tx));
+      certified = ((c[0] >> wave) & 1) != 0;      // (wave-uniform: a scalar load and a scalar shift)
+    }
   } else {
     int cxi, cyi;
     wg_corner_tap<KIND, NF>(img, map, tx, yblk, lane, &cxi, &cyi);
@@ -906,7 +915,11 @@ __device__ __forceinline__ void remap_wg_body(const ImageArgs& img, const MapArg
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
-  if (rows > 0) {
+  if (PLAN && certified) {
+    // a whole, unclipped tile (the certificate says so): exact radial factor on the node rows, the cubic through them on the others;
+    // the fill's six loads go out in front of the four node rows and the first two interpolated ones
+    if constexpr (PLAN) radial_rows_interp<NF>(map, rowtab, col, xf, yf, [&](auto jc) { issue_fill(jc); });
+  } else if (rows > 0) {
     if (KIND == kRadial || !map.fast_div) {
       if (unclipped) rows_1(std::true_type{}, I0{});
       else rows_1(std::false_type{}, I0{});
@@ -1084,9 +1097,9 @@ __device__ __forceinline__ void remap_wg_body(const ImageArgs& img, const MapArg
 // (runtime-length coefficient vectors -- NF < 0 -- walk the vector in LDS and need more registers than six waves per SIMD leave: at six
 // they spilled 116-148 bytes into scratch, and every reload of a spill is a VMEM wait that also waits for the untracked fill;
 // tools/isa_hazards.py keeps the shipped instantiations free of scratch)
-template <int KIND, int NF, int SAMPLER, typename T = float>
+template <int KIND, int NF, int SAMPLER, typename T = float, bool PLAN = false>
 __global__ void __launch_bounds__(256, (NF < 0 ? 4 : (NF == 1 ? 5 : DCP_WG_WAVES))) remap_wg_kernel(const ImageArgs img, const MapArgs map) {
-  remap_wg_body<KIND, NF, SAMPLER, T>(img, map);
+  remap_wg_body<KIND, NF, SAMPLER, T, PLAN>(img, map);
 }
 
 // ------------------------------------------------------------------ K1, many frames in one launch
@@ -1164,6 +1177,66 @@ __global__ void __launch_bounds__(64) box_table_kernel(const ImageArgs img0, con
   MapArgs map;
   batch_frame_args<NF>(img0, tab, blockIdx.z, &img, &map);
   tile_hull<kRadial, NF>(img, map, blockIdx.z, boxes);
+}
+
+// ------------------------------------------------------------------ K1, frame plans
+
+// The plan of one calibration and frame shape (frame_plan.cpp): workgroups and waves laid out as in remap_wg_body, plain tile order.
+// Every wave takes the hull of its workgroup tile exactly as a wave of remap_wg_kernel without a table does (wg_corner_tap) and
+// evaluates its 16 coordinate rows twice, with map_coord as phase 1 does and with radial_rows_interp, the function the frame kernel
+// calls for a certified tile.  The wave tile's certificate bit is set only if all 2 048 float32 values have the same bit patterns
+// AND the tile is one that phase 1 would run unclipped and whole -- the box fits the slab and lies strictly inside the image, 16 rows,
+// 64 columns.  Everything else (the frame's border, partial tiles, the tile that holds the centre, where ru has its kink) keeps the
+// exact evaluation.  Words [0, 4n): hulls, [4n, 5n): certificate bits (bit w = wave w of the tile).
+template <int NF>
+__global__ void __launch_bounds__(256) plan_table_kernel(const ImageArgs img, const MapArgs map, int32_t* plan) {
+  __shared__ double s_row[4][kLdsTH][2];
+  __shared__ int s_ok[4];
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int lane = (int)threadIdx.x & 63;
+  const int wx = wave & 1, wy = wave >> 1;
+  const int tx = blockIdx.x, ty = blockIdx.y;
+  const int yblk = ty * kWgTH;
+  const int y0 = yblk + wy * kLdsTH;
+  const int x = tx * kWgTW + wx * kLdsTW + lane;
+  const float wmaxf = (float)(img.W - 1), hmaxf = (float)(img.H - 1);
+  int cxi, cyi;
+  wg_corner_tap<kRadial, NF>(img, map, tx, yblk, lane, &cxi, &cyi);
+  const int xa = __builtin_amdgcn_readlane(cxi, 0), xb = __builtin_amdgcn_readlane(cxi, 1);
+  const int xc_ = __builtin_amdgcn_readlane(cxi, 2), xd_ = __builtin_amdgcn_readlane(cxi, 3);
+  const int ya = __builtin_amdgcn_readlane(cyi, 0), yb = __builtin_amdgcn_readlane(cyi, 1);
+  const int yc_ = __builtin_amdgcn_readlane(cyi, 2), yd_ = __builtin_amdgcn_readlane(cyi, 3);
+  const int cx0 = min(min(xa, xb), min(xc_, xd_)), cx1 = max(max(xa, xb), max(xc_, xd_));
+  const int cy0 = min(min(ya, yb), min(yc_, yd_)), cy1 = max(max(ya, yb), max(yc_, yd_));
+  // as remap_wg_body<.., float> has them
+  const int bx0 = max(min(cx0 - 1, img.W - 2), 0), bx1 = min(cx1 + 2, img.W - 1);
+  const int by0 = max(min(cy0 - 1, img.H - 2), 0), by1 = min(cy1 + 2, img.H - 1);
+  const bool fits = bx1 - bx0 + 1 <= kWgBoxW && by1 - by0 + 1 <= kWgBoxH;
+  const bool box_inside = cx0 - 1 >= 0 && cx1 + 2 <= img.W - 1 && cy0 - 1 >= 0 && cy1 + 2 <= img.H - 1;
+  const int rows = max(0, min(kLdsTH, img.rows_out - y0));
+  const bool whole = fits && box_inside && rows == kLdsTH && tx * kWgTW + wx * kLdsTW + kLdsTW <= img.W;      // wave-uniform
+  int ok = 0;
+  if (whole) {
+    if (lane < kLdsTH) fill_row<kRadial, 2>(map, s_row[wave], lane, (double)(img.y_origin + min(y0 + lane, img.rows_out - 1)));
+    const ColCtx col = make_col<kRadial, NF>(map, min(x, img.W - 1));
+    float xi[kLdsTH], yi[kLdsTH];
+    radial_rows_interp<NF>(map, s_row[wave], col, xi, yi, [](auto) {});
+    bool equal = true;
+#pragma unroll
+    for (int k = 0; k < kLdsTH; ++k) {
+      double xd, yd;
+      map_coord<kRadial, NF, 2, 0>(map, s_row[wave], nullptr, col, k, wmaxf, hmaxf, &xd, &yd);
+      equal = equal && __float_as_uint((float)xd) == __float_as_uint(xi[k]) && __float_as_uint((float)yd) == __float_as_uint(yi[k]);
+    }
+    ok = __builtin_amdgcn_ballot_w64(equal) == ~0ull ? 1 : 0;
+  }
+  if (lane == 0) s_ok[wave] = ok;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const size_t ntiles = (size_t)img.tiles_x * img.tiles_y, t = (size_t)ty * img.tiles_x + tx;
+    *(int4*)(plan + 4 * t) = make_int4(cx0, cx1, cy0, cy1);
+    plan[4 * ntiles + t] = s_ok[0] | (s_ok[1] << 1) | (s_ok[2] << 2) | (s_ok[3] << 3);
+  }
 }
 
 // ------------------------------------------------------------------ K5: explicit coordinates
@@ -1881,6 +1954,13 @@ static hipError_t launch_lds(const ImageArgs& img_in, const MapArgs& map, hipStr
   return hipGetLastError();
 }
 
+// (PlanBuildFn of frame_plan.cpp: img as launch_wg has it -- tiles_x / tiles_y of remap_wg_kernel)
+template <int NF>
+static hipError_t launch_plan_table(const ImageArgs& img, const MapArgs& map, int32_t* plan, hipStream_t stream) {
+  hipLaunchKernelGGL((plan_table_kernel<NF>), dim3(img.tiles_x, img.tiles_y), dim3(256), 0, stream, img, map, plan);
+  return hipGetLastError();
+}
+
 template <int KIND, int NF, int SAMPLER>
 static hipError_t launch_wg(const ImageArgs& img_in, const MapArgs& map, hipStream_t stream) {
   ImageArgs img = img_in;
@@ -1895,6 +1975,21 @@ static hipError_t launch_wg(const ImageArgs& img_in, const MapArgs& map, hipStre
   unsigned pad = 0;
   if (img.wg_per_cu >= 1 && img.wg_per_cu <= 5) pad = (unsigned)(160 * 1024 / img.wg_per_cu - 24 * 1024) & ~255u;
   note_kernel("remap_wg_kernel", KIND, NF, SAMPLER);
+  if constexpr (KIND == kRadial && NF >= 0) {
+    // the calibration's frame plan, if it has one by now (frame_plan.cpp): hulls and certificate bits from its table.  While the plan may
+    // still be under construction on the device, the launch keeps its barrier bit whatever the caller allows.
+    bool ordered = false;
+    if (const int32_t* plan = frame_plan_lookup(img, map, stream, &launch_plan_table<NF>, &ordered)) {
+      img.boxes = plan;
+      if (pad > 32768u) {
+        const hipError_t e = hipFuncSetAttribute((const void*)remap_wg_kernel<KIND, NF, SAMPLER, float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
+        if (e != hipSuccess) return e;
+      }
+      if (ordered) hipLaunchKernelGGL((remap_wg_kernel<KIND, NF, SAMPLER, float, true>), grid, dim3(256), pad, stream, img, map);
+      else DCP_LAUNCH_FRAME((remap_wg_kernel<KIND, NF, SAMPLER, float, true>), grid, dim3(256), pad, stream, img, map);
+      return hipGetLastError();
+    }
+  }
   if (pad > 32768u) {        // beyond the 64 KB a launch may ask for by default (static 24.6 KB + the padding)
     const hipError_t e = hipFuncSetAttribute((const void*)remap_wg_kernel<KIND, NF, SAMPLER, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
     if (e != hipSuccess) return e;

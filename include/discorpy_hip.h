@@ -70,7 +70,8 @@ const char* dcp_last_error(void);
 
 /* Device scratch the library keeps between calls -- the calling thread's staging buffers and streams for
  * DCP_MEM_HOST calls (grow-only, otherwise freed when the thread ends) and the per-device float64 planes of the
- * spline path -- is released; the next call allocates again.  For long-running services. */
+ * spline path, and the per-calibration frame plans of every device (the devices are synchronised first) -- is released; the next
+ * call allocates again.  For long-running services. */
 int dcp_release_scratch(void);
 
 /* Options (process-wide).  The documented ones:

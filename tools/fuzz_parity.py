@@ -358,6 +358,9 @@ def main():
         F.set_option("x_stack_wg", (2, 1, 2, 0)[k % 4])     # workgroup-box stack kernel: whenever eligible / automatic / off
         F.set_option("x_wg_box", 0 if k % 5 == 4 else 1)    # one box per workgroup, or per wave tile
         F.set_option("tile_cert", 0 if k % 7 == 6 else 1) # the host certificate, or the per-pixel vote
+        F.set_option("x_frame_plan", 2 if k % 2 else 0)   # remap_wg_kernel on a frame plan built at first sight, or without one
+        if k % 32 == 31:
+            F.release_scratch()                             # (every case is a new calibration: hand the replaced plans back now and then)
         launched.clear()
         kind = one_case(rng, k)
         counts[kind] = counts.get(kind, 0) + 1
@@ -367,6 +370,7 @@ def main():
     bounds = F.debug_bounds()
     for key in ("x_stack_lds", "x_stack_wg", "x_wg_box", "tile_cert"):
         F.set_option(key, 1)
+    F.set_option("x_frame_plan", 1)
     print("fuzz_parity: %d cases (seed %d) all equal in %.1f s: %s; cases in which each kernel ran: %s; LDS-kernel fallbacks exercised: "
           "%d tiles did not fit, %d tiles failed the vote" % (cases, seed, time.time() - t0, dict(sorted(counts.items())),
                                                               dict(sorted(kernels.items())), nofit, vote))
