@@ -1971,9 +1971,11 @@ static hipError_t launch_wg(const ImageArgs& img_in, const MapArgs& map, hipStre
   // four, 7 % slower than the plain order.  Stripes when the widest XCD carries at most 7 % more than the average.
   if (img.xcd_remap == 2 && 8 * ((img.tiles_x + 7) / 8) * 100 > img.tiles_x * 107) img.xcd_remap = 0;
   const dim3 grid(img.xcd_remap == 2 ? 8 * ((img.tiles_x + 7) / 8) : img.tiles_x, img.tiles_y);
-  // workgroups per CU capped through unused dynamic LDS (the static 23.5 KB allow six): img.wg_per_cu in 1..5
+  // workgroups per CU capped through unused dynamic LDS (the static 25 608 bytes -- slab, row tables -- allow six): img.wg_per_cu in 1..5.
+  // 26 KB stand for the static part, so that static and padding together fit the CU's 160 KB / wg_per_cu: with less set aside
+  // wg_per_cu = 1 asks for more LDS than a CU has (the launch is refused) and 2..5 each fit one workgroup fewer than they say.
   unsigned pad = 0;
-  if (img.wg_per_cu >= 1 && img.wg_per_cu <= 5) pad = (unsigned)(160 * 1024 / img.wg_per_cu - 24 * 1024) & ~255u;
+  if (img.wg_per_cu >= 1 && img.wg_per_cu <= 5) pad = (unsigned)(160 * 1024 / img.wg_per_cu - 26 * 1024) & ~255u;
   note_kernel("remap_wg_kernel", KIND, NF, SAMPLER);
   if constexpr (KIND == kRadial && NF >= 0) {
     // the calibration's frame plan, if it has one by now (frame_plan.cpp): hulls and certificate bits from its table.  While the plan may

@@ -24,6 +24,8 @@ def _cases():
     return {
         "cfg2_4096": ((4096, 4096), c2["xcenter"], c2["ycenter"], c2["list_fact"]),
         "cfg4_model_2560": ((2560, 2560), x4, y4, f4),
+        # (nine coefficients, but the host certifies config 5 for 64 x 16 tiles only -- level 1: like the strong model below it runs on
+        # remap_lds_kernel and exercises no plan; NF = 9 on a plan: tests/test_frame_plan_coverage.py)
         "cfg5_8192_nf9": ((8192, 8192), c5["xcenter"], c5["ycenter"], c5["list_fact"]),
         # (certified for 64 x 16 tiles only: runs on remap_lds_kernel, which has no plan -- the result must be equal all the same)
         "strong_1280x1000": ((1000, 1280), 500.3, 400.7, [1.0, -1e-4, 3e-7, -2e-10, 1e-13]),
