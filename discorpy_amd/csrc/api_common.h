@@ -149,8 +149,9 @@ static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPer
 // One description of every single-frame call (api_image.cpp make_frame_call validates it, run_frame executes it), as StackCall
 // is of every stack call.  Executors: the tuned float32 kernels within 32-bit offsets (unwarp_kernels.hip), the generic ones for
 // orders 0 / 1 on any element type (typed_kernels.hip, or remap_wg_kernel / the one-channel colour kernel where they qualify),
-// interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip).
-enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline };
+// interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip), the forward scatter of any element
+// type (api_spline.cpp for its winner plane, forward_kernels.hip).
+enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline, kExecForward };
 struct FrameCall {
   FrameExec exec;
   dcp::MapKind kind;
@@ -214,5 +215,8 @@ int host_round_trip(const HostTrip& t, hipStream_t st, Launch&& launch) {
 
 // api_spline.cpp: the spline executor (c.exec == kExecSpline; the device is selected)
 int run_spline(const FrameCall& c);
+// api_spline.cpp: the forward-scatter executor (c.exec == kExecForward; the device is selected); its winner plane is leased from the
+// spline workspace
+int run_forward(const FrameCall& c);
 
 }  // namespace dcpapi

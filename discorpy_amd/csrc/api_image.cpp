@@ -1,5 +1,5 @@
 // api_image.cpp -- single-frame entry points of the C ABI: radial / perspective / fused remaps, explicit coordinates,
-// interleaved channels, points and coordinate maps, on float32 and the other element types, orders 0..5.  Every frame call
+// interleaved channels, the forward scatter, points and coordinate maps, on float32 and the other element types, orders 0..5.  Every frame call
 // is described once (FrameCall, make_frame_call) and executed by run_frame; spline orders by api_spline.cpp's run_spline.
 #include "api_common.h"
 
@@ -402,6 +402,17 @@ int make_frame_call(FrameCall* c, FrameExec exec, dcp::MapKind kind, const void*
   c->device = device;
   c->stream = (hipStream_t)stream;
   const bool cert = g_tile_cert.load() != 0;
+  if (exec == kExecForward) {
+    // the scatter moves elements of any type; its winner plane indexes pixels with 32 bits (0 = vacant)
+    if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
+    if ((double)H * (double)W >= 4294967295.0)
+      return fail(DCP_ERR_UNSUPPORTED, "forward unwarp of %lld x %lld pixels: the winner plane indexes at most 2^32 - 2 of them", (long long)H,
+                  (long long)W);
+    const char *s0 = (const char*)src, *s1 = s0 + extent_bytes_typed(H, W, rs, cs, dtype);
+    const char *d0 = (const char*)dst, *d1 = d0 + (size_t)H * (size_t)W * (size_t)dcp::elem_size(dtype);
+    if (s0 < d1 && d0 < s1) return fail(DCP_ERR_INVALID_ARG, "source and destination overlap: a scatter cannot run in place");
+    return DCP_OK;
+  }
   if (exec == kExecColour) {
     if (channels < 1 || channels > 64) return fail(DCP_ERR_INVALID_ARG, "channels = %d outside [1, 64]", channels);
     if (order < 0 || order > 1) return fail(DCP_ERR_UNSUPPORTED, "the interleaved-channel kernels take orders 0 and 1 (got %d)", order);
@@ -529,6 +540,7 @@ int run_frame(const FrameCall& c) {
   DeviceScope scope(c.device);
   if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", c.device, hipGetErrorString(scope.status));
   if (c.exec == kExecSpline) return run_spline(c);
+  if (c.exec == kExecForward) return run_forward(c);
   if (!c.host) {
     DCP_HIP(launch_frame(c, c.src, c.dst, c.ycoord, c.xcoord, c.rs, c.cs, 0, 0, c.stream));
     return DCP_OK;
@@ -612,6 +624,48 @@ int map_points(dcp::MapKind kind, const double* yx_in, double* yx_out, int64_t n
   t.row_bytes = t.pitch = t.out_bytes = (size_t)npts * 16;
   t.dst = yx_out;
   return host_round_trip(t, st, [&](const void* din, void* dout, void*, void*) { return launch(din, dout); });
+}
+
+// dcp_map_points_inverse_f64: as map_points, with the count of points without a root delivered where the points live
+int map_points_inverse(const double* yx_in, double* yx_out, int64_t npts, double xc, double yc, const double* fact, int nfact,
+                       int64_t* n_unsolved, int mem_kind, int device, void* stream) {
+  int rc;
+  bool host = false;
+  if ((rc = mem_kind_of(mem_kind, &host)) != DCP_OK) return rc;
+  if (npts < 0) return fail(DCP_ERR_INVALID_ARG, "npts < 0");
+  if (npts > 0 && (!yx_in || !yx_out)) return fail(DCP_ERR_INVALID_ARG, "null point pointer");
+  dcp::MapArgs map;
+  if ((rc = frame_map(&map, dcp::kRadial, xc, yc, fact, nfact, nullptr, 0, 0)) != DCP_OK) return rc;
+  if (npts == 0 && (host || !n_unsolved)) {
+    if (n_unsolved) *n_unsolved = 0;
+    return DCP_OK;
+  }
+  DeviceScope scope(device);
+  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
+  hipStream_t st = (hipStream_t)stream;
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
+  auto launch = [&](const void* in, void* out, void* count) -> hipError_t {
+    if (count) {
+      const hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), st);
+      if (e != hipSuccess) return e;
+    }
+    return dcp::launch_map_points_inverse((const double*)in, (double*)out, npts, map, (unsigned long long*)count, st);
+  };
+  if (!host) {
+    DCP_HIP(launch(yx_in, yx_out, n_unsolved));
+    return DCP_OK;
+  }
+  int64_t count = 0, unused = 0;
+  HostTrip t;
+  t.src = yx_in;
+  t.row_bytes = t.pitch = t.out_bytes = (size_t)npts * 16;
+  t.dst = yx_out;
+  t.y_down = &count;                     // the counter travels as an 8-byte plane (slot 2; slot 3 comes back unread)
+  t.x_down = &unused;
+  t.plane = sizeof(int64_t);
+  rc = host_round_trip(t, st, [&](const void* din, void* dout, void* dcount, void*) { return launch(din, dout, dcount); });
+  if (rc == DCP_OK && n_unsolved) *n_unsolved = count;
+  return rc;
 }
 
 }  // namespace
@@ -802,6 +856,15 @@ int dcp_unwarp_color_image(const void* src, void* dst, int dtype, int64_t height
   return rc != DCP_OK ? rc : run_frame(c);
 }
 
+int dcp_unwarp_image_forward(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
+                             int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact, int nfact, int mem_kind,
+                             int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecForward, dcp::kRadial, src, dst, dtype, height, width, src_row_stride, src_col_stride, 1, xcenter,
+                                 ycenter, list_fact, nfact, nullptr, Points{}, 0, DCP_BLEND_SCIPY, 0, 0, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
 int dcp_unwarp_image_spline_f32(const float* src, float* dst, int64_t height, int64_t width, int64_t src_row_stride,
                                 int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact,
                                 int nfact, int order, int boundary_mode, int mem_kind, int device, void* stream) {
@@ -848,6 +911,11 @@ int dcp_remap_coords_spline_f32(const float* src, float* dst, int64_t height, in
 int dcp_map_points_f64(const double* yx_in, double* yx_out, int64_t npts, double xcenter, double ycenter,
                        const double* list_fact, int nfact, int mem_kind, int device, void* stream) {
   return map_points(dcp::kRadial, yx_in, yx_out, npts, xcenter, ycenter, list_fact, nfact, nullptr, mem_kind, device, stream);
+}
+
+int dcp_map_points_inverse_f64(const double* yx_in, double* yx_out, int64_t npts, double xcenter, double ycenter,
+                               const double* list_fact, int nfact, int64_t* n_unsolved, int mem_kind, int device, void* stream) {
+  return map_points_inverse(yx_in, yx_out, npts, xcenter, ycenter, list_fact, nfact, n_unsolved, mem_kind, device, stream);
 }
 
 int dcp_map_points_perspective_f64(const double* yx_in, double* yx_out, int64_t npts, const double* list_coef, int mem_kind, int device,

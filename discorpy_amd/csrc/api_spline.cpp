@@ -1,5 +1,6 @@
 // api_spline.cpp -- spline orders 2..5 (scipy's prefiltered B-spline interpolation, spline_kernels.hip): the
-// per-device coefficient workspace and the spline executor of FrameCall (api_image.cpp holds the entry points).
+// per-device coefficient workspace and the spline executor of FrameCall (api_image.cpp holds the entry points).  The forward
+// scatter (forward_kernels.hip) leases its winner plane from the same workspace: run_forward.
 #include "api_common.h"
 
 #include <cmath>
@@ -214,6 +215,48 @@ int run_spline(const FrameCall& c) {
     ca.ycoord = dy;
     ca.xcoord = dx;
     return dcp::launch_spline(a, c.kind, c.map, ca, ddst, st);
+  });
+}
+
+// unwarp_image_forward: the winner plane (H W words) comes from the spline workspace -- a slot per stream, so calls on different streams
+// scatter into different planes --, then the two launches on the call's stream.  Host memory: the source goes up whole (a scatter
+// reaches any row: no bands), the dense result comes back.
+int run_forward(const FrameCall& c) {
+  hipStream_t st = c.stream;
+  int cur_dev = 0;
+  DCP_HIP(hipGetDevice(&cur_dev));                           // (run_frame has selected it)
+  if (cur_dev < 0 || cur_dev >= 64) return fail(DCP_ERR_UNSUPPORTED, "device index %d", cur_dev);
+  SplineWorkspace::Slot* slot = nullptr;
+  DCP_HIP(g_spline_ws.acquire((size_t)c.H * (size_t)c.W * sizeof(uint32_t), st, cur_dev, &slot));
+  SlotGuard guard{slot, st};
+  dcp::ForwardArgs a;
+  memset(&a, 0, sizeof(a));
+  a.winner = (uint32_t*)slot->buf;
+  a.H = (int32_t)c.H;
+  a.W = (int32_t)c.W;
+  a.esize = dcp::elem_size(c.dtype);
+  a.src_stride = c.rs;
+  a.src_cstride = c.cs;
+  if (!c.host) {
+    a.src = c.src;
+    a.dst = c.dst;
+    DCP_HIP(dcp::launch_forward(a, c.map, st));
+    return DCP_OK;
+  }
+  const size_t esz = (size_t)a.esize;
+  const bool pack = c.cs == 1;                                // unit column stride: the rows are packed on the way up
+  HostTrip t;
+  t.src = c.src;
+  t.row_bytes = pack ? (size_t)c.W * esz : extent_bytes_typed(c.H, c.W, c.rs, c.cs, c.dtype);
+  t.rows = pack ? (size_t)c.H : 1;
+  t.pitch = pack ? (size_t)c.rs * esz : t.row_bytes;
+  t.dst = c.dst;
+  t.out_bytes = (size_t)c.H * (size_t)c.W * esz;
+  return host_round_trip(t, st, [&](const void* dsrc, void* ddst, void*, void*) {
+    a.src = dsrc;
+    a.dst = ddst;
+    if (pack) a.src_stride = c.W;
+    return dcp::launch_forward(a, c.map, st);
   });
 }
 

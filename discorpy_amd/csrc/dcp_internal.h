@@ -231,6 +231,22 @@ hipError_t launch_typed_stack(const TypedStackArgs& st, const MapArgs& map, hipS
 hipError_t launch_map_points(const double* yx_in, double* yx_out, int64_t n, const MapArgs& map, hipStream_t stream);
 // n points (y, x) through the homography map.coef (numpy's operation order), float64
 hipError_t launch_map_points_persp(const double* yx_in, double* yx_out, int64_t n, const MapArgs& map, hipStream_t stream);
+// n points (y, x) -> centre + (ru / rd) (p - centre), ru the root of ru B(ru) = rd (safeguarded Newton, float64); a point without a
+// root becomes NaN and adds one to *n_unsolved (device memory, zeroed by the caller on `stream`; nullptr: not counted)
+hipError_t launch_map_points_inverse(const double* yx_in, double* yx_out, int64_t n, const MapArgs& map, unsigned long long* n_unsolved,
+                                     hipStream_t stream);
+// forward_kernels.hip: the forward scatter of unwarp_image_forward (discorpy/post/postprocessing.py:151-185).  Source pixel s = y W + x
+// goes to d = yu W + xu; `winner` (H W words, zeroed by the launcher on `stream`) keeps the greatest s + 1 per destination, the fill
+// pass moves the winners' elements (esize = 1, 2, 4 or 8 bytes; source strides in elements, dense destination).  H W < 2^32 - 1.
+struct ForwardArgs {
+  const void* src;
+  void* dst;
+  uint32_t* winner;
+  int64_t src_stride, src_cstride;
+  int32_t H, W;
+  int32_t esize;
+};
+hipError_t launch_forward(const ForwardArgs& a, const MapArgs& map, hipStream_t stream);
 // interleaved (H, W, C) image, radial map, orders 0 / 1; src_cstride = elements between pixels
 hipError_t launch_typed_channels(const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
 // color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, certified radial map);

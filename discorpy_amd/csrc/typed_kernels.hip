@@ -13,6 +13,8 @@
 //                                 d_chunk projections; unwarp_slice_backward keeps float64
 //                                 coordinates and stores float32, unwarp_chunk_slices_backward rounds
 //                                 the coordinates to float32 and stores T
+//   map_points_*_kernel           lists of points, float64: the radial model, its inverse (the root of ru B(ru) = rd) and the
+//                                 homography -- one thread per point
 //
 // Plain 64-bit addressing (no 4 GiB limit), no LDS staging: float32 is the hot path and has its own
 // kernels (unwarp_kernels.hip); these are HBM-bound gathers with 1..8-byte taps.
@@ -240,6 +242,84 @@ hipError_t launch_map_points(const double* yx_in, double* yx_out, int64_t n, con
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(map_points_kernel, dim3((unsigned)((n + kTypedBlock - 1) / kTypedBlock)), dim3(kTypedBlock), 0, stream,
                      yx_in, yx_out, n, map);
+  return hipGetLastError();
+}
+
+// Inverse of the radial mapping for a list of points (unwarp_line_backward, discorpy/post/postprocessing.py:72-108): the reference
+// minimises (rd - ru B(ru))^2 from ru = rd; this finds the root of g(ru) = ru B(ru) - rd itself.  Newton from ru = rd; as soon as
+// two iterates of opposite sign bracket a root every step that leaves the bracket (or has no finite Newton step) is replaced by its
+// midpoint.  Done when g == 0 or a step no longer moves ru by more than two units in the last place; of the iterates the one with
+// the smallest |g| is kept.  out = centre + (ru / rd) (p - centre) in the reference's operation order, the centre itself for rd == 0.
+// No root within the budget, or only a negative one: NaN, counted in *n_unsolved.
+constexpr int kInverseBudget = 100;
+
+__global__ void __launch_bounds__(kTypedBlock) map_points_inverse_kernel(const double* __restrict__ yx_in, double* __restrict__ yx_out,
+                                                                          int64_t n, const MapArgs map, unsigned long long* n_unsolved) {
+  const int64_t i = (int64_t)blockIdx.x * kTypedBlock + threadIdx.x;
+  if (i >= n) return;
+  const double y = yx_in[2 * i], x = yx_in[2 * i + 1];
+  const double xd = x - map.xc, yd = y - map.yc;
+  const double rd = sqrt_rn(xd * xd + yd * yd);
+  if (rd == 0.0) {
+    yx_out[2 * i] = map.yc + 0.0 * yd;
+    yx_out[2 * i + 1] = map.xc + 0.0 * xd;
+    return;
+  }
+  const double kEps = 2.220446049250313e-16;
+  double ru = rd, best = rd, best_g = __builtin_inf();
+  double neg = 0.0, pos = 0.0;           // iterates with g < 0 / g > 0
+  bool has_neg = false, has_pos = false, solved = false;
+  for (int it = 0; it < kInverseBudget && rd == rd; ++it) {
+    double B = 0.0, dB = 0.0;            // B(ru) and B'(ru), Horner from the highest power
+    for (int k = map.nfact - 1; k >= 0; --k) {
+      dB = __builtin_fma(dB, ru, B);
+      B = __builtin_fma(B, ru, map.fact[k]);
+    }
+    const double g = __builtin_fma(ru, B, -rd), dg = __builtin_fma(ru, dB, B);
+    if (!(__builtin_fabs(g) <= 1.7e308)) break;                 // overflow or NaN: no way on from here
+    if (__builtin_fabs(g) < best_g) {
+      best_g = __builtin_fabs(g);
+      best = ru;
+    }
+    if (g == 0.0) {
+      solved = true;
+      break;
+    }
+    if (g < 0.0) {
+      neg = ru;
+      has_neg = true;
+    } else {
+      pos = ru;
+      has_pos = true;
+    }
+    const bool bracket = has_neg && has_pos;
+    const double lo = neg < pos ? neg : pos, hi = neg < pos ? pos : neg;
+    double rn = ru - g / dg;
+    if (bracket && !(rn > lo && rn < hi)) rn = 0.5 * (lo + hi);          // (also a NaN / infinite Newton step)
+    if (!(__builtin_fabs(rn) <= 1.7e308)) break;                          // no bracket and no Newton step
+    if (__builtin_fabs(rn - ru) <= 2.0 * kEps * __builtin_fabs(rn) || (bracket && hi - lo <= 2.0 * kEps * __builtin_fabs(hi))) {
+      solved = true;
+      break;
+    }
+    ru = rn;
+  }
+  if (!solved || !(best >= 0.0)) {
+    const double nan = __builtin_nan("");
+    yx_out[2 * i] = nan;
+    yx_out[2 * i + 1] = nan;
+    if (n_unsolved) atomicAdd(n_unsolved, 1ull);
+    return;
+  }
+  const double factor = best / rd;
+  yx_out[2 * i] = map.yc + factor * yd;
+  yx_out[2 * i + 1] = map.xc + factor * xd;
+}
+
+hipError_t launch_map_points_inverse(const double* yx_in, double* yx_out, int64_t n, const MapArgs& map, unsigned long long* n_unsolved,
+                                     hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(map_points_inverse_kernel, dim3((unsigned)((n + kTypedBlock - 1) / kTypedBlock)), dim3(kTypedBlock), 0, stream,
+                     yx_in, yx_out, n, map, n_unsolved);
   return hipGetLastError();
 }
 

@@ -1,17 +1,23 @@
-"""MI355X drop-in for the remap functions of ``discorpy.post.postprocessing``.
+"""MI355X drop-in for ``discorpy.post.postprocessing``: every public function of the reference's module is here.
 
 Same names, positional arguments, defaults and error messages as the reference
 (``/root/reference/discorpy/post/postprocessing.py``):
 
+* :func:`unwarp_line_forward`           reference lines 36-64
+* :func:`unwarp_line_backward`          reference lines 72-108
 * :func:`unwarp_image_backward`         reference lines 111-148
+* :func:`unwarp_image_forward`          reference lines 151-185
 * :func:`unwarp_slice_backward`         reference lines 188-229
 * :func:`unwarp_chunk_slices_backward`  reference lines 255-313
+* :func:`calc_residual_hor`, :func:`calc_residual_ver`, :func:`check_distortion`   reference lines 316-411
+* :func:`correct_perspective_line`      reference lines 414-441
 * :func:`correct_perspective_image`     reference lines 462-492
 
 plus :func:`unwarp_perspective_fused`, the one-pass composition BASELINE config 3 asks for.
 
-Every call runs a hand-written HIP kernel through the C ABI of ``libdiscorpy_hip.so``
-(``include/discorpy_hip.h``).  There is no CPU path: a missing library or GPU raises.
+Every image, stack and point-list call runs a hand-written HIP kernel through the C ABI of ``libdiscorpy_hip.so``
+(``include/discorpy_hip.h``).  There is no CPU path: a missing library or GPU raises.  The three assessment helpers
+(residuals of a few hundred points, a threshold) are NumPy, as in the reference.
 
 Inputs may be
 
@@ -38,7 +44,13 @@ What differs from the reference, on purpose:
   dtype; without it NumPy outputs are leased from a recycling pool (``discorpy_amd/_pool.py``) so that
   a loop does not pay 4 ms of page faults per 4096 x 4096 frame; ``blend`` selects the bilinear arithmetic (``"f64lerp"`` default: float64
   factorised lerp, within one float32 ulp of scipy and bit-equal in practice; ``"scipy"``:
-  scipy's exact float64 operation order; ``"f32"``: float32 lerp, opt-in).
+  scipy's exact float64 operation order; ``"f32"``: float32 lerp, opt-in);
+* :func:`unwarp_image_forward` is the reference's scatter bit for bit wherever no coordinate lies within rounding (~1e-11 px) of a
+  half-integer -- the greatest source index wins a contested pixel, as NumPy's assignment order has it -- but a centre or
+  coefficient that is not finite raises ``ValueError`` (the reference turns such coordinates into undefined integers);
+* :func:`unwarp_line_backward` solves ``ru * B(ru) = rd`` itself (safeguarded Newton, to rounding) where the reference minimises
+  the squared difference (``scipy.optimize.minimize``, ~1e-6 px short of the root); a point for which the model has no root raises
+  ``ValueError`` with the count, where the reference returns the minimiser.
 """
 import ctypes as C
 import os
@@ -48,7 +60,8 @@ import numpy as np
 from .. import _ffi as F
 from .. import _pool
 
-__all__ = ["unwarp_line_forward", "unwarp_image_backward", "unwarp_images_backward", "unwarp_slice_backward", "unwarp_chunk_slices_backward",
+__all__ = ["unwarp_line_forward", "unwarp_line_backward", "unwarp_image_forward", "calc_residual_hor", "calc_residual_ver",
+           "check_distortion", "correct_perspective_line", "unwarp_image_backward", "unwarp_images_backward", "unwarp_slice_backward", "unwarp_chunk_slices_backward",
            "unwarp_slice_backward_centres", "unwarp_chunk_slices_backward_centres",
            "correct_perspective_image", "unwarp_perspective_fused", "remap_coordinates",
            "generate_radial_map", "generate_fused_map"]
@@ -348,6 +361,187 @@ def unwarp_line_forward(list_lines, xcenter, ycenter, list_fact):
         pos += n
         res.append(uline)
     return res
+
+
+def unwarp_line_backward(list_lines, xcenter, ycenter, list_fact):
+    """
+    Unwarp lines of dot-centroids using a backward model (reference ``postprocessing.py:72-108``): the undistorted
+    point of each distorted one, i.e. the radius ``ru`` with ``ru * B(ru) = rd``.
+
+    Parameters
+    ----------
+    list_lines : list of 2D arrays
+        (y, x) coordinates of the dot-centroids of each line.
+    xcenter, ycenter : float
+        Center of distortion.
+    list_fact : list of floats
+        Polynomial coefficients of the backward model.
+
+    Returns
+    -------
+    list of 2D arrays
+        The unwarped (y, x) coordinates, line by line, in each line's dtype.  All points of all lines go through one launch
+        (``dcp_map_points_inverse_f64``), which finds the root itself (Newton safeguarded by bisection) -- the reference
+        minimises the squared difference numerically and stops ~1e-6 px short of it.
+
+    Raises
+    ------
+    ValueError
+        If the model has no root for some points (it folds there, or never reaches their radius); the message names how
+        many.  The reference returns the minimiser of the squared difference for such points.
+    """
+    lines = [np.asarray(line) for line in list_lines]
+    fa, nf = F.fact_array(_coefs(list_fact, "list_fact"))
+    sizes = [len(line) for line in lines]
+    if sum(sizes) == 0:
+        return [np.zeros_like(line) for line in lines]
+    pts = np.ascontiguousarray(np.concatenate([line[:, :2].reshape(-1, 2) for line in lines if len(line)]), dtype=np.float64)
+    out = np.empty_like(pts)
+    unsolved = C.c_int64(0)
+    F.require_device()
+    F.check(F.lib().dcp_map_points_inverse_f64(pts.ctypes.data, out.ctypes.data, pts.shape[0], float(xcenter), float(ycenter), fa, nf,
+                                               C.byref(unsolved), F.MEM_HOST, int(os.environ.get("DISCORPY_AMD_DEVICE", "-1")), None))
+    if unsolved.value > 0:
+        raise ValueError("the backward model has no root for %d of %d points (it folds or never reaches their radius)"
+                         % (unsolved.value, pts.shape[0]))
+    res, pos = [], 0
+    for line, n in zip(lines, sizes):
+        uline = np.zeros_like(line)                  # the reference keeps the input's dtype (np.zeros_like)
+        if n:
+            uline[:, 0] = out[pos:pos + n, 0]
+            uline[:, 1] = out[pos:pos + n, 1]
+        pos += n
+        res.append(uline)
+    return res
+
+
+def unwarp_image_forward(mat, xcenter, ycenter, list_fact, *, out=None):
+    """
+    Unwarp an image using a forward model (reference ``postprocessing.py:151-185``).  Should be used only for assessment
+    due to the problem of vacant pixels.
+
+    Every pixel is moved to the rounded, clipped position the forward model gives it; where several pixels meet, the one
+    with the greatest row-major index stays (the order of NumPy's assignment in the reference), and pixels nobody reaches
+    are zero.  Pixels are copied, never computed with.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array (NumPy array, ROCm torch tensor or ``__cuda_array_interface__`` device array) of any element type the other
+        image functions take (float32 / float64, 8- to 64-bit integers, bool; complex through its parts).
+    xcenter : float
+        Center of distortion in x-direction.
+    ycenter : float
+        Center of distortion in y-direction.
+    list_fact : list of floats
+        Polynomial coefficients of the forward model.
+    out : array_like, optional
+        Destination of the same kind, shape and dtype; must not overlap ``mat``.
+
+    Returns
+    -------
+    array_like
+        2D array. Distortion-corrected image, same kind and dtype as the input.
+
+    Raises
+    ------
+    ValueError
+        If the centre or a coefficient is not finite (the reference converts such coordinates to undefined integers), or if
+        ``out`` overlaps ``mat``.
+    """
+    (height, width) = mat.shape
+    parts = _complex_parts(mat)
+    if parts is not None:
+        res = parts[2](unwarp_image_forward(parts[0], xcenter, ycenter, list_fact),
+                       unwarp_image_forward(parts[1], xcenter, ycenter, list_fact))
+        if out is not None:
+            out[...] = res
+            return out
+        return res
+    fact = _coefs(list_fact, "list_fact")
+    if not np.all(np.isfinite([float(xcenter), float(ycenter)] + fact)):
+        raise ValueError("unwarp_image_forward needs a finite centre and finite coefficients")
+    img = _Image(mat, 2).dense_rows()
+    fa, nf = F.fact_array(fact)
+    out, optr = img.empty((height, width), out=out)
+    F.require_device()
+    F.check(F.lib().dcp_unwarp_image_forward(img.ptr, optr, img.code, height, width, img.strides[0], img.strides[1],
+                                             float(xcenter), float(ycenter), fa, nf, img.mem, img.device, img.stream))
+    return out
+
+
+def _line_residuals(list_ulines, xcenter, ycenter, horizontal):
+    """Per line: the least-squares straight line through its points (y on x for a horizontal line, x on y for a vertical
+    one), then each point's distance to that line next to its distance to the centre; all pairs sorted by radius."""
+    pairs = []
+    for line in list_ulines:
+        line = np.asarray(line)
+        dy, dx = line[:, 0] - ycenter, line[:, 1] - xcenter
+        along, across = (dx, dy) if horizontal else (dy, dx)
+        slope, intercept = np.polyfit(along, across, 1)
+        dist = np.abs(slope * along - across + intercept) / np.sqrt(slope ** 2 + 1)
+        pairs.append(np.column_stack((np.sqrt(dx ** 2 + dy ** 2), dist)))
+    data = np.concatenate(pairs) if pairs else np.zeros((0, 2))
+    return data[data[:, 0].argsort()]
+
+
+def calc_residual_hor(list_ulines, xcenter, ycenter):
+    """
+    Distances of unwarped dots on each horizontal line to the straight line fitted through that line: the straightness of
+    the unwarped lines (reference ``postprocessing.py:316-351``).  NumPy on the host: a few hundred numbers.
+
+    Parameters
+    ----------
+    list_ulines : list of 2D arrays
+        (y, x) coordinates of the dot-centroids on each unwarped horizontal line.
+    xcenter, ycenter : float
+        Center of distortion.
+
+    Returns
+    -------
+    array_like
+        2D array of (distance of a dot to the centre of distortion, distance of the dot to its fitted line), sorted by the
+        first.
+    """
+    return _line_residuals(list_ulines, xcenter, ycenter, True)
+
+
+def calc_residual_ver(list_ulines, xcenter, ycenter):
+    """
+    The same for vertical lines, fitted as x on y (reference ``postprocessing.py:354-388``).
+
+    Parameters
+    ----------
+    list_ulines : list of 2D arrays
+        (y, x) coordinates of the dot-centroids on each unwarped vertical line.
+    xcenter, ycenter : float
+        Center of distortion.
+
+    Returns
+    -------
+    array_like
+        2D array of (distance of a dot to the centre of distortion, distance of the dot to its fitted line), sorted by the
+        first.
+    """
+    return _line_residuals(list_ulines, xcenter, ycenter, False)
+
+
+def check_distortion(list_data):
+    """
+    Is the distortion significant?  True when more than 15 % of the dots lie further than 1 pixel from their fitted line
+    (reference ``postprocessing.py:391-411``).
+
+    Parameters
+    ----------
+    list_data : array_like
+        (radius, residual) of each dot, as :func:`calc_residual_hor` / :func:`calc_residual_ver` return it.
+
+    Returns
+    -------
+    bool
+    """
+    residuals = np.asarray(list_data)[:, 1]
+    return bool(np.count_nonzero(residuals > 1.0) / len(residuals) > 0.15)
 
 
 def correct_perspective_line(list_lines, list_coef):

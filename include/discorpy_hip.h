@@ -305,6 +305,17 @@ int dcp_unwarp_fused_spline_f32(const float* src, float* dst, int64_t height, in
 int dcp_unwarp_image_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
                            int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
                            int order, int boundary_mode, int mem_kind, int device, void* stream);
+/* discorpy/post/postprocessing.py:151-185 (unwarp_image_forward): every source pixel (y, x) is MOVED to
+ *   (yu, xu) = rint(clip(centre + F(rd) * (p - centre), 0, size - 1)),  F(rd) = sum_i list_fact[i] * rd^i,
+ * float64 throughout, rint rounding half to even as np.round does.  Where several source pixels meet, the one with the greatest
+ * row-major index y * width + x stays (NumPy's assignment order); destinations nobody reaches are all-zero bytes.  Elements are
+ * copied, never computed with: any DCP_DTYPE_*, NaN payloads and -0.0 included.  dst is dense (height x width) and must not overlap
+ * src.  A coordinate that is not a number goes to index 0.  Two launches (forward_winner_kernel: one 32-bit atomic maximum per source
+ * pixel into a height * width word plane of the library's per-stream workspace; forward_fill_kernel) on `stream`; host memory is
+ * staged whole.  height * width >= 2^32 - 1: DCP_ERR_UNSUPPORTED. */
+int dcp_unwarp_image_forward(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,
+                             int64_t src_col_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
+                             int mem_kind, int device, void* stream);
 int dcp_perspective_image_typed(const void* src, void* dst, int dtype, int64_t height, int64_t width,
                                 int64_t src_row_stride, int64_t src_col_stride, const double* list_coef, int order,
                                 int boundary_mode, int mem_kind, int device, void* stream);
@@ -375,6 +386,16 @@ int dcp_coordinate_map_f32(float* ymap, float* xmap, int64_t height, int64_t wid
  * reference's numpy/libm evaluation to a few units in the last place. */
 int dcp_map_points_f64(const double* yx_in, double* yx_out, int64_t npts, double xcenter, double ycenter,
                        const double* list_fact, int nfact, int mem_kind, int device, void* stream);
+
+/* discorpy/post/postprocessing.py:72-108 (unwarp_line_backward): the INVERSE of the mapping above for npts points given as (y, x)
+ * pairs of doubles -- out = centre + (ru / rd) * (p - centre), where rd = |p - centre| and ru solves ru * B(ru) = rd with
+ * B(r) = sum_i list_fact[i] * r^i (Newton from ru = rd, bisection once a sign change is bracketed, a fixed iteration budget; the
+ * centre maps to itself).  The reference minimises the squared difference with scipy.optimize.minimize and leaves ~1e-6 px of the
+ * equation unsolved; this is the root to rounding.  A point for which no root >= 0 is found (the model folds there, or has no
+ * solution) is written as NaN and counted: *n_unsolved (optional) receives the count and lives where the points live -- host memory
+ * for DCP_MEM_HOST, device memory (written on `stream`) for DCP_MEM_DEVICE. */
+int dcp_map_points_inverse_f64(const double* yx_in, double* yx_out, int64_t npts, double xcenter, double ycenter,
+                               const double* list_fact, int nfact, int64_t* n_unsolved, int mem_kind, int device, void* stream);
 
 /* discorpy/post/postprocessing.py:414-441 (correct_perspective_line): the homography applied to npts points given as (y, x) pairs of
  * doubles -- xn = (c1 x + c2 y + c3) / (c7 x + c8 y + 1), yn = (c4 x + c5 y + c6) / (c7 x + c8 y + 1) in numpy's operation order with

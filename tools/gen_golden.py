@@ -3,7 +3,7 @@
 
 Runs only in the build container (the reference never travels to the GPU box).  Each fixture
 holds the inputs (or the seed that regenerates them) and the reference's outputs; nothing of the
-reference's source is stored.  SURVEY.md section 8(c) lists the cases G1..G9.
+reference's source is stored.  SURVEY.md section 8(c) lists the cases G1..G9; the later sets are described where they are made.
 
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
 """
@@ -35,7 +35,7 @@ def save(name, **arrays):
     if os.path.exists(path):
         old = np.load(path)
         if sorted(old.files) == sorted(arrays) and all(
-                np.asarray(arrays[k]).dtype == old[k].dtype and np.array_equal(old[k], arrays[k], equal_nan=True)
+                np.asarray(arrays[k]).dtype == old[k].dtype and np.array_equal(old[k], arrays[k], equal_nan=old[k].dtype.kind in "fc")
                 for k in arrays):
             print("%-28s unchanged" % (name + ".npz"))
             return
@@ -528,4 +528,110 @@ def g20():
 
 
 g20()
+
+
+# G21: unwarp_image_forward (postprocessing.py:151-185), the scatter mat_unw[yu_mat, xu_mat] = mat.  Inputs come from
+# tests/helpers/forward_emulation.py (g21_input: seeded frames, full-range element types, floats with NaN payloads and -0.0); the
+# fixture keeps the parameters and the reference's outputs.  Every case that is not a tie case must keep all its unrounded coordinates
+# at least 1e-9 px from a half-integer -- the kernels evaluate the polynomial in another order than NumPy (~4e-16 relative, < 1e-11 px
+# on these frames), and only with that margin is bit equality with the reference a fair demand.  The margins are stored.
+def g21():
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import forward_emulation as fe
+    out = {}
+    for name in fe.g21_names():
+        mat, xc, yc, fact = fe.g21_input(name)
+        res = post.unwarp_image_forward(mat, xc, yc, fact)
+        assert res.dtype == mat.dtype and res.shape == mat.shape
+        margin = fe.half_integer_margin(mat.shape[0], mat.shape[1], xc, yc, fact)
+        if name.startswith("tie_"):
+            assert margin == 0.0, (name, margin)
+        else:
+            assert margin >= 1e-9, "G21 case %s: a coordinate lies %.3g px from a half-integer; choose another model" % (name, margin)
+        out["out_" + name], out["margin_" + name] = res, f64(margin)
+        out["shape_" + name], out["xcenter_" + name], out["ycenter_" + name], out["list_fact_" + name] = (
+            np.array(mat.shape), f64(xc), f64(yc), f64(fact))
+    _, _, yf, xf = fe.forward_destinations(41, 57, 0.0, 0.0, [0.5])
+    out["ties_tie_half"] = np.int64(np.count_nonzero((np.abs(yf - np.floor(yf) - 0.5) == 0) | (np.abs(xf - np.floor(xf) - 0.5) == 0)))
+    assert out["ties_tie_half"] > 1000
+    save("g21_forward_images", **out)
+
+
+g21()
+
+
+# G22: unwarp_line_backward (postprocessing.py:72-108; scipy.optimize.minimize per point) under two monotone models: the lines of the
+# reference's own unit test (tests/test_postprocessing.py:36-59, 69-75) and a 15 x 20 grid over a 900 x 1200 frame plus the centre
+# itself.  `*_dlines` = the grid under the model in NumPy (the reference test's construction), `*_ref` = the reference's answer,
+# `*_min_dg` = the minimum of g'(ru) = sum (i + 1) a_i ru^i over [0, 1.01 max radius]: by the mean value theorem two radii whose
+# equation residuals are e1 and e2 lie within (|e1| + |e2|) / min g' of each other.
+def g22():
+    def warp(lines, xc, yc, fact):
+        res = []
+        for line in lines:
+            xu, yu = line[:, 1] - xc, line[:, 0] - yc
+            ru = np.sqrt(xu ** 2 + yu ** 2)
+            fl = np.sum(np.asarray([a * ru ** i for i, a in enumerate(fact)]), axis=0)
+            res.append(np.asarray(list(zip(yc + yu * fl, xc + xu * fl))))
+        return res
+
+    out = {}
+    unit = [np.asarray([[64 - y, x] for x in np.arange(1, 64, 2.0)]) for y in np.arange(1, 64, 2.0)]
+    grid = [np.asarray([[y, x] for x in np.linspace(3.0, 1195.0, 20)]) for y in np.linspace(2.0, 897.0, 15)]
+    grid.append(np.asarray([[450.7, 600.2]]))                                     # the centre itself
+    for name, lines, xc, yc, fact in (("unit", unit, 33.5, 35.5, [1.0, -2.0e-3]), ("grid", grid, 600.2, 450.7, [1.0, 2.0e-4, 3.0e-7])):
+        dlines = warp(lines, xc, yc, fact)
+        ref = post.unwarp_line_backward(dlines, xc, yc, fact)
+        rmax = max(np.sqrt((ln[:, 1] - xc) ** 2 + (ln[:, 0] - yc) ** 2).max() for ln in list(ref) + list(lines))
+        r = np.linspace(0.0, 1.01 * rmax, 20001)
+        dg = np.sum(np.asarray([(i + 1) * a * r ** i for i, a in enumerate(fact)]), axis=0)
+        assert dg.min() > 0.1, (name, dg.min())                                   # monotone, with room
+        out[name + "_xcenter"], out[name + "_ycenter"], out[name + "_list_fact"] = f64(xc), f64(yc), f64(fact)
+        out[name + "_ulines"] = np.concatenate(lines)
+        out[name + "_dlines"] = np.concatenate(dlines)
+        out[name + "_ref"] = np.concatenate(ref)
+        out[name + "_sizes"] = np.array([len(ln) for ln in lines])
+        out[name + "_min_dg"] = f64(dg.min())
+    save("g22_lines_backward", **out)
+
+
+g22()
+
+
+# G23: calc_residual_hor / calc_residual_ver / check_distortion (postprocessing.py:316-411) on warped and on corrected lines of the
+# reference's unit test (tests/test_postprocessing.py:36-59, 125-157), both outcomes of the check present; and the names of the
+# public functions of the reference's post module.
+def g23():
+    import inspect
+    xc, yc = 33.5, 35.5
+    hor = [np.asarray([[64 - y, x] for x in np.arange(1, 64, 2.0)]) for y in np.arange(1, 64, 2.0)]
+    ver = [np.asarray([[64 - y, x] for y in np.arange(1, 64, 2.0)]) for x in np.arange(1, 64, 2.0)]
+
+    def warp(lines, fact):
+        res = []
+        for line in lines:
+            xu, yu = line[:, 1] - xc, line[:, 0] - yc
+            ru = np.sqrt(xu ** 2 + yu ** 2)
+            fl = np.sum(np.asarray([a * ru ** i for i, a in enumerate(fact)]), axis=0)
+            res.append(np.asarray(list(zip(yc + yu * fl, xc + xu * fl))))
+        return res
+
+    out = dict(xcenter=f64(xc), ycenter=f64(yc))
+    sets = {"hor_warped": (warp(hor, [1.0, -2.0e-2]), post.calc_residual_hor),
+            "hor_corrected": (post.unwarp_line_forward(warp(hor, [1.0, -2.0e-3]), xc, yc, [1.0, 2.0e-3]), post.calc_residual_hor),
+            "ver_warped": (warp(ver, [1.0, -2.0e-2]), post.calc_residual_ver),
+            "ver_corrected": (post.unwarp_line_forward(warp(ver, [1.0, -2.0e-3]), xc, yc, [1.0, 2.0e-3]), post.calc_residual_ver)}
+    checks = []
+    for name, (lines, fn) in sets.items():
+        res = fn(lines, xc, yc)
+        out[name + "_lines"], out[name + "_residuals"] = np.asarray(lines), res
+        out[name + "_check"] = np.bool_(post.check_distortion(res))
+        checks.append(bool(out[name + "_check"]))
+    assert True in checks and False in checks
+    out["public_names"] = np.array(sorted(n for n, f in inspect.getmembers(post, inspect.isfunction)
+                                          if f.__module__ == post.__name__ and not n.startswith("_")))
+    save("g23_residuals", **out)
+
+
+g23()
 print("done")
