@@ -127,6 +127,8 @@ int homography_is_tame(const double* c, int64_t H, int64_t W);
 // *tall_ok (optional): radial maps -- the bound also holds for 64 x 32 tiles and (nearly) all their source boxes fit 80 x 56
 // (remap_wg_color_kernel's tile shape for sheared maps)
 int tile_deviation_certified(int kind, const dcp::MapArgs& m, int64_t H, int64_t W, int* tall_ok = nullptr);
+// level 2 of the above and the boxes of 128 x 16 tiles inside remap_wg_color_kernel's slab (homography and fused map)
+bool colour_boxes_fit(int kind, const dcp::MapArgs& m, int64_t H, int64_t W);
 // yd = yc + B(r) yu increases with yu at every x over the frame (sufficient test): no row of a chunk can then leave the
 // band the reference crops from the chunk's first and last rows
 bool radial_monotone_in_y(const dcp::MapArgs& m, int64_t H, int64_t W);

@@ -242,6 +242,7 @@ struct CertEntry {
   int64_t H = 0, W = 0;
   double xc = 0, yc = 0, fact[dcp::kMaxFact], coef[8];
   int ok = 0, tall = 0;
+  int colour = -1;     // colour_boxes_fit's answer for this entry (-1: not asked yet)
 };
 thread_local CertEntry g_cert_cache[kCertSlots];
 thread_local int g_cert_next = 0, g_cert_last = 0;
@@ -343,8 +344,19 @@ int tile_deviation_certified(int kind, const dcp::MapArgs& m, int64_t H, int64_t
   memcpy(c.coef, m.coef, sizeof(c.coef));
   c.ok = ok;
   c.tall = tall;
+  c.colour = -1;
   if (tall_ok) *tall_ok = tall;
   return ok;
+}
+
+// remap_wg_color_kernel under a homography or the fused map: the level-2 certificate (its bound for 128 x 32 tiles covers the
+// kernel's 128 x 16 ones) and (nearly) every such tile's source box inside the colour slab of 144 pixels x 26 rows -- the rule
+// level 2 itself applies to remap_wg_kernel's slab.  Kept with the certificate's cache entry.
+bool colour_boxes_fit(int kind, const dcp::MapArgs& m, int64_t H, int64_t W) {
+  if (tile_deviation_certified(kind, m, H, W) < 2) return false;
+  CertEntry& c = g_cert_cache[g_cert_last];        // (the entry the call above found or made)
+  if (c.colour < 0) c.colour = wg_boxes_mostly_fit(kind, m, H, W, 128, 16, 144.0, 26.0) ? 1 : 0;
+  return c.colour == 1;
 }
 
 // d/dyu [B(r) yu] = B + B' yu^2 / r >= B - |B'| r: positive on [0, rmax] => every column's row coordinate increases with

@@ -424,7 +424,8 @@ int make_frame_call(FrameCall* c, FrameExec exec, dcp::MapKind kind, const void*
       return fail(DCP_ERR_INVALID_ARG, "row stride %lld overlaps rows of %lld pixels", (long long)rs, (long long)W);
     // float32 only: the one-ulp factorisation; integer types always blend in scipy's exact order (their rounding ties depend on it)
     c->sampler = order == 0 ? dcp::kNearest : (blend_mode == DCP_BLEND_F64LERP && dtype == dcp::kF32 ? dcp::kF64Lerp : dcp::kScipy);
-    c->map.tile_dev_ok = cert ? tile_deviation_certified(dcp::kRadial, c->map, H, W) : 0;
+    if (kind == dcp::kRadial) c->map.tile_dev_ok = cert ? tile_deviation_certified(dcp::kRadial, c->map, H, W) : 0;
+    else c->map.tile_dev_ok = cert && (kind != dcp::kFused || g_fused_wg.load()) && colour_boxes_fit(kind, c->map, H, W) ? 2 : 0;
     return DCP_OK;
   }
   if (exec == kExecTuned) {
@@ -503,7 +504,7 @@ hipError_t launch_frame(const FrameCall& c, const void* src, void* dst, const vo
   bool taken = false;
   if (c.exec == kExecColour) {
     // the workgroup-box kernel (remap_wg_color_kernel) where the call qualifies -- dense pixels of 3 / 4 channels, float32 / uint8 /
-    // uint16, certified map --, else one thread per pixel
+    // uint16, map of any kind certified --, else one thread per pixel
     const double ext = ((double)(c.H - 1) * (double)rs + (double)(c.W - 1) * (double)cs + (double)c.channels) * (double)dcp::elem_size(c.dtype);
     a.blend = c.sampler;
     a.y0 = (int32_t)y0;
@@ -512,10 +513,10 @@ hipError_t launch_frame(const FrameCall& c, const void* src, void* dst, const vo
       img.src_bytes = (uint32_t)ext;
       img.y_origin = a.y0;
       img.rows_out = a.rows;
-      const hipError_t e = dcp::launch_color(img, c.map, c.channels, c.dtype, c.sampler, c.opts, s, &taken);
+      const hipError_t e = dcp::launch_color(c.kind, img, c.map, c.channels, c.dtype, c.sampler, c.opts, s, &taken);
       if (e != hipSuccess || taken) return e;
     }
-    return dcp::launch_typed_channels(a, c.map, c.channels, s);
+    return dcp::launch_typed_channels(c.kind, a, c.map, c.channels, s);
   }
   // 8- / 16-bit integers, radial or perspective map, certified: the workgroup-box kernel (same arithmetic, LDS-staged); 4- and
   // 8-byte element types under a radial map: the interleaved-pixel kernel with one channel (color_kernels.hip)
@@ -526,7 +527,7 @@ hipError_t launch_frame(const FrameCall& c, const void* src, void* dst, const vo
     img.src_bytes = (uint32_t)extent_bytes_typed(c.H, c.W, rs, 1, c.dtype);
     img.xcd_remap = c.opts.xcd_remap;
     const hipError_t e = c.kind == dcp::kRadial && (c.dtype == dcp::kF64 || c.dtype == dcp::kI32 || c.dtype == dcp::kU32)
-                             ? dcp::launch_color(img, mapc, 1, c.dtype, c.order == 0 ? dcp::kNearest : dcp::kScipy, c.opts, s, &taken)
+                             ? dcp::launch_color(dcp::kRadial, img, mapc, 1, c.dtype, c.order == 0 ? dcp::kNearest : dcp::kScipy, c.opts, s, &taken)
                              : dcp::launch_wg_typed(c.kind, img, mapc, c.order, c.dtype, c.opts, s, &taken);
     if (e != hipSuccess || taken) return e;
   }
@@ -550,10 +551,12 @@ int run_frame(const FrameCall& c) {
   if (tuned_image || c.exec == kExecColour) {
     const bool dense = tuned_image ? c.cs == 1 && c.W >= 2 : c.cs == c.channels;
     // radial float32 bands go through the stack kernel (a band of image rows = a chunk of rows of a one-projection stack)
+    // (interleaved channels under a homography travel in bands only when it is tame: band_source_rows takes the band's hull from its corners)
     const bool stack_bands = tuned_image && c.kind == dcp::kRadial && c.sampler != dcp::kNearest && c.round_f32;
     void* alias = nullptr;
     const HostPath path = host_path(c.H, (double)c.H * (double)c.W * (double)pix, dense && tuned_image && (c.kind == dcp::kRadial || c.map.fast_div),
-                                    dense && (!tuned_image || stack_bands || (c.kind != dcp::kRadial && c.map.fast_div)), c.dst, &alias);
+                                    dense && (tuned_image ? stack_bands || (c.kind != dcp::kRadial && c.map.fast_div) : c.kind == dcp::kRadial || c.map.fast_div),
+                                    c.dst, &alias);
     auto hull = [&](int64_t r0, int64_t n, int64_t* b0, int64_t* b1) { band_source_rows(c.kind, c.map, c.H, c.W, r0, n, b0, b1); };
     auto band = [&](void* dsrc, void* dband, int64_t r0, int64_t n, hipStream_t s) {
       return launch_frame(c, dsrc, dband, nullptr, nullptr, c.W * c.channels, c.channels, r0, n, s);
@@ -853,6 +856,24 @@ int dcp_unwarp_color_image(const void* src, void* dst, int dtype, int64_t height
   FrameCall c;
   const int rc = make_frame_call(&c, kExecColour, dcp::kRadial, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
                                  xcenter, ycenter, list_fact, nfact, nullptr, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_perspective_color_image(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                int64_t src_pixel_stride, const double* list_coef, int order, int blend_mode, int mem_kind, int device,
+                                void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColour, dcp::kPersp, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels, 0.0,
+                                 0.0, nullptr, 0, list_coef, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_unwarp_fused_color_image(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                 int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
+                                 const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColour, dcp::kFused, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
+                                 xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
   return rc != DCP_OK ? rc : run_frame(c);
 }
 

@@ -3,8 +3,11 @@
 // channel -- C calls of scipy.ndimage.map_coordinates on the views mat_pad[:, :, i], all at the SAME coordinates
 // (utility.py:320-341).  Here a pixel's coordinate is evaluated once and its C channels are blended together.
 //
-//   remap_wg_color_kernel<NF, SAMPLER, T, NC>   remap_wg_kernel's data path (unwarp_kernels.hip) for pixels of NC
-//                                               interleaved elements of type T
+//   remap_wg_color_kernel<KIND, NF, SAMPLER, T, NC>   remap_wg_kernel's data path (unwarp_kernels.hip) for pixels of NC
+//                                                     interleaved elements of type T
+//
+// KIND: the radial map; or the homography / the one-pass perspective -> radial map of the reference's demos, which loop
+// post.correct_perspective_image over mat[:, :, i] (examples/readthedocs_demo/demo_07.py:25,60; demo_05.py:127,147).
 //
 // A workgroup of four waves owns a 128 x 16 output tile (2 x 2 wave sub-tiles of 64 x 8 pixels).  Its source box --
 // the hull of the tile's four corner pixels grown by one pixel, under the host's level-2 tile certificate
@@ -14,7 +17,9 @@
 // and stores them with one NC-element store, so a wave's store is 64 NC sizeof(T) contiguous bytes.
 // Bound: HBM / the L2 -> L1 stream, 2 NC sizeof(T) algorithmic bytes per pixel (24 for float32 RGB); ~80 VALU
 // instructions per RGB pixel against ~45 for one plane, so the arithmetic hides under the memory stream more easily
-// than in the single-plane kernel.  No MFMA: a remap, not a contraction.
+// than in the single-plane kernel.  No MFMA: a remap, not a contraction.  The homography adds a correctly rounded float64 division
+// per pixel and the fused map the radial chain behind it (75 VALU instructions per pixel in the single-plane kernel): paid once for
+// all NC channels here.
 //
 // Arithmetic: identical to remap_wg_kernel's per channel -- float64 coordinate, rounded to float32 and clipped
 // (utility.py:316-317), then scipy's order-1 blend (SAMPLER = kScipy: bit-equal to the reference), its one-ulp
@@ -163,17 +168,60 @@ __device__ __forceinline__ void store_pixel(const T (&v)[NC], __amdgpu_buffer_rs
   }
 }
 
+// Workgroups per CU the register allocation aims at (one wave per SIMD and workgroup): what the kernel's LDS lets a CU of 160 KB
+// hold -- the slab, the per-wave row tables (RW doubles per row: 2 under the radial map, 4 under a homography) and the coefficient
+// table of the looped polynomial, rounded up to the allocation granule (1280 B is the coarsest a 160 KB CU hands out; a finer
+// granule only leaves room to spare) -- and never more than three: float32 x 3 (45 056 + 1 024 + 256 B -> 47 360) fits three
+// times under either row table, float32 x 4 (61 440 B of slab) twice, the narrower pixels are not bound by LDS.
+template <int KIND, int NF, typename T, int NC, int SHAPE>
+constexpr int color_wg_per_cu() {
+  constexpr int kRowTab = 4 * kColRPW * (KIND == kRadial ? 2 : 4) * 8, kCoefTab = (NF < 0 ? kMaxFact : 1) * 8;
+  constexpr int kLds = (ColorGeom<T, NC, SHAPE>::kSlabBytes + kRowTab + kCoefTab + 1279) / 1280 * 1280;
+  return 3 * kLds <= 160 * 1024 ? 3 : 2;
+}
+
+// Corner `corner` (bit 0: right, bit 1: bottom) of the workgroup tile (tx, yblk / TH): its source pixel, rounded and clipped as the
+// taps are -- wg_corner_tap of unwarp_kernels.hip for this kernel's tile shapes.  kFused (lanes 0..3 together, corner = lane): the
+// radial map at the corners of the bounding box of the tile's four clipped perspective positions (see there for why that hull holds).
+template <int KIND, int NF, int SHAPE>
+__device__ __forceinline__ void color_corner_tap(const ImageArgs& img, const MapArgs& map, int tx, int yblk, int corner, int* cxi, int* cyi) {
+  using S = TileShape<SHAPE>;
+  const float wmaxf = (float)(img.W - 1), hmaxf = (float)(img.H - 1);
+  const double X = (double)min(tx * S::TW + (corner & 1) * (S::TW - 1), img.W - 1);
+  const double Y = (double)(img.y_origin + min(yblk + ((corner >> 1) & 1) * (S::TH - 1), img.rows_out - 1));
+  double xd, yd;
+  if constexpr (KIND == kFused) {
+    double px, py;
+    corner_coord<kPersp, NF>(map, X, Y, &px, &py);
+    const float pxf = round_clip_f32(px, wmaxf), pyf = round_clip_f32(py, hmaxf);
+    float qx[4], qy[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      qx[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxf), i));
+      qy[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pyf), i));
+    }
+    const float qx0 = fminf(fminf(qx[0], qx[1]), fminf(qx[2], qx[3])), qx1 = fmaxf(fmaxf(qx[0], qx[1]), fmaxf(qx[2], qx[3]));
+    const float qy0 = fminf(fminf(qy[0], qy[1]), fminf(qy[2], qy[3])), qy1 = fmaxf(fmaxf(qy[0], qy[1]), fmaxf(qy[2], qy[3]));
+    corner_coord<kRadial, NF>(map, (double)((corner & 1) ? qx1 : qx0), (double)((corner & 2) ? qy1 : qy0), &xd, &yd);
+  } else {
+    corner_coord<KIND, NF>(map, X, Y, &xd, &yd);
+  }
+  *cxi = (int)round_clip_f32(xd, wmaxf);
+  *cyi = (int)round_clip_f32(yd, hmaxf);
+}
+
 // ImageArgs as for remap_wg_kernel, with src / dst reinterpreted as T*, src_stride = ELEMENTS between source rows, src_col_stride =
 // NC (dense pixels), src_bytes the extent in bytes, W / H in PIXELS; the result is dense (W NC elements per row).
-template <int NF, int SAMPLER, typename T, int NC, int SHAPE = 0>
-__global__ void __launch_bounds__(256, (ColorGeom<T, NC, SHAPE>::kSlabBytes <= 53 * 1024 ? 3 : 2)) remap_wg_color_kernel(const ImageArgs img, const MapArgs map) {
+template <int KIND, int NF, int SAMPLER, typename T, int NC, int SHAPE = 0>
+__global__ void __launch_bounds__(256, (color_wg_per_cu<KIND, NF, T, NC, SHAPE>())) remap_wg_color_kernel(const ImageArgs img, const MapArgs map) {
   using G = ColorGeom<T, NC, SHAPE>;
   using S = TileShape<SHAPE>;
   constexpr int kColTW = S::TW, kColTH = S::TH, kColBoxH = S::BoxH;
   constexpr int ES = G::ES, PS = G::PS, CH = G::CH, PB = G::PB, NJ = G::NJ;
   constexpr int RPW = kColRPW;
+  constexpr int RW = KIND == kRadial ? 2 : 4;      // doubles per row of the row table (fill_row: 2 radial, 3 of 4 under a homography)
   __shared__ __attribute__((aligned(16))) unsigned char s_box[G::kSlabBytes];
-  __shared__ double s_row[4][RPW][2];
+  __shared__ double s_row[4][RPW][RW];
   __shared__ double s_coef[NF < 0 ? kMaxFact : 1];
   const T* const srcT = (const T*)img.src;
   T* const dstT = (T*)img.dst;
@@ -201,11 +249,8 @@ __global__ void __launch_bounds__(256, (ColorGeom<T, NC, SHAPE>::kSlabBytes <= 5
   // ---- the tile's four corner pixels, one per lane 0..3, by every wave for itself (no exchange, no barrier)
   int cx0, cx1, cy0, cy1;
   {
-    const double X = (double)min(tx * kColTW + (lane & 1) * (kColTW - 1), img.W - 1);
-    const double Y = (double)(img.y_origin + min(yblk + ((lane >> 1) & 1) * (kColTH - 1), img.rows_out - 1));
-    double xd, yd;
-    corner_coord<kRadial, NF>(map, X, Y, &xd, &yd);
-    const int cxi = (int)round_clip_f32(xd, wmaxf), cyi = (int)round_clip_f32(yd, hmaxf);
+    int cxi, cyi;
+    color_corner_tap<KIND, NF, SHAPE>(img, map, tx, yblk, lane, &cxi, &cyi);
     const int xa = __builtin_amdgcn_readlane(cxi, 0), xb = __builtin_amdgcn_readlane(cxi, 1);
     const int xc_ = __builtin_amdgcn_readlane(cxi, 2), xd_ = __builtin_amdgcn_readlane(cxi, 3);
     const int ya = __builtin_amdgcn_readlane(cyi, 0), yb = __builtin_amdgcn_readlane(cyi, 1);
@@ -244,14 +289,14 @@ __global__ void __launch_bounds__(256, (ColorGeom<T, NC, SHAPE>::kSlabBytes <= 5
   };
 
   // ---- row table of this wave's rows (same-wave LDS traffic is ordered: no barrier)
-  if (lane < RPW) fill_row<kRadial, 2>(map, s_row[wave], lane, (double)(img.y_origin + min(y0 + lane, img.rows_out - 1)));
-  if constexpr (NF < 0) {
+  if (lane < RPW) fill_row<KIND, RW>(map, s_row[wave], lane, (double)(img.y_origin + min(y0 + lane, img.rows_out - 1)));
+  if constexpr (NF < 0 && KIND != kPersp) {
     if ((int)threadIdx.x < map.nfact) s_coef[threadIdx.x] = map.fact[threadIdx.x];
     __syncthreads();
   }
   const int rows = __builtin_amdgcn_readfirstlane(max(0, min(RPW, img.rows_out - y0)));
   const int ybase = __builtin_amdgcn_readfirstlane(min(y0, img.rows_out - 1));
-  const ColCtx col = make_col<kRadial, NF>(map, min(x, img.W - 1));
+  const ColCtx col = make_col<KIND, NF>(map, min(x, img.W - 1));
   const auto* rowtab = s_row[wave];
   const uint32_t row_bytes_out = (uint32_t)img.W * (uint32_t)PS;
   const char* out_base = (const char*)dstT + (size_t)ybase * (size_t)row_bytes_out;
@@ -261,15 +306,23 @@ __global__ void __launch_bounds__(256, (ColorGeom<T, NC, SHAPE>::kSlabBytes <= 5
   // ---- phase 1: the source coordinates of the sub-tile's rows, the loads of the fill going out between them
   float xf[RPW], yf[RPW];
   constexpr int kPerRow = (NJ + RPW - 1) / RPW;              // loads in front of every coordinate row
-  if (rows > 0) {
+  auto rows_1 = [&](auto fastdiv) {                // (the homography's division fixed at compile time, as in remap_wg_kernel)
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
 #pragma unroll
       for (int q = 0; q < kPerRow; ++q) issue_fill(k * kPerRow + q);
       double xd, yd;
-      map_coord<kRadial, NF, 2, 0>(map, rowtab, s_coef, col, k, wmaxf, hmaxf, &xd, &yd);
+      map_coord<KIND, NF, RW, decltype(fastdiv)::value>(map, rowtab, s_coef, col, k, wmaxf, hmaxf, &xd, &yd);
       xf[k] = round_clip_f32(xd, wmaxf);
       yf[k] = round_clip_f32(yd, hmaxf);
+    }
+  };
+  if (rows > 0) {
+    if constexpr (KIND == kRadial) {
+      rows_1(std::integral_constant<int, 0>{});
+    } else {
+      if (map.fast_div) rows_1(std::integral_constant<int, 1>{});
+      else rows_1(std::integral_constant<int, 0>{});
     }
   } else {
 #pragma unroll
@@ -370,7 +423,7 @@ __global__ void __launch_bounds__(256, (ColorGeom<T, NC, SHAPE>::kSlabBytes <= 5
 
 DCP_DEFINE_BOUNDS_READER(read_bounds_color)
 
-template <int NF, int SAMPLER, typename T, int NC, int SHAPE = 0>
+template <int KIND, int NF, int SAMPLER, typename T, int NC, int SHAPE = 0>
 static hipError_t launch_color_t(const ImageArgs& img_in, const MapArgs& map, hipStream_t stream) {
   using S = TileShape<SHAPE>;
   ImageArgs img = img_in;
@@ -380,11 +433,13 @@ static hipError_t launch_color_t(const ImageArgs& img_in, const MapArgs& map, hi
   if (img.xcd_remap != 2 || 8 * ((img.tiles_x + 7) / 8) * 100 > img.tiles_x * 107) img.xcd_remap = 0;
   const dim3 grid(img.xcd_remap == 2 ? 8 * ((img.tiles_x + 7) / 8) : img.tiles_x, img.tiles_y);
   char name[96];
-  snprintf(name, sizeof(name), "remap_wg_color_kernel<NF=%d,%s,%s x %d%s>", NF, SAMPLER == kNearest ? "nearest" : SAMPLER == kScipy ? "scipy" : "f64lerp",
+  // (the radial map is not named: its kernels keep the names they had before the other maps came; as the single-plane names otherwise)
+  snprintf(name, sizeof(name), "remap_wg_color_kernel<%sNF=%d,%s,%s x %d%s>", KIND == kRadial ? "" : KIND == kPersp ? "Persp," : "Fused,", NF,
+           SAMPLER == kNearest ? "nearest" : SAMPLER == kScipy ? "scipy" : "f64lerp",
            std::is_same<T, float>::value ? "float32" : std::is_same<T, double>::value ? "float64" : std::is_same<T, int32_t>::value ? "int32"
            : std::is_same<T, uint32_t>::value ? "uint32" : sizeof(T) == 2 ? "uint16" : "uint8", NC, SHAPE == 1 ? ",64x32 tiles" : "");
   set_last_kernel_name(name);
-  hipLaunchKernelGGL((remap_wg_color_kernel<NF, SAMPLER, T, NC, SHAPE>), grid, dim3(256), 0, stream, img, map);
+  hipLaunchKernelGGL((remap_wg_color_kernel<KIND, NF, SAMPLER, T, NC, SHAPE>), grid, dim3(256), 0, stream, img, map);
   return hipGetLastError();
 }
 
@@ -397,48 +452,61 @@ static MapArgs pad_to(const MapArgs& m, int n) {
   return p;
 }
 
-template <int SAMPLER, typename T, int NC, int SHAPE = 0>
+template <int KIND, int SAMPLER, typename T, int NC, int SHAPE = 0>
 static hipError_t launch_color_n(const ImageArgs& img, const MapArgs& map, hipStream_t stream) {
-  if (map.nfact <= 5) return launch_color_t<5, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 5), stream);
-  if (map.nfact <= 10) return launch_color_t<10, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 10), stream);
-  return launch_color_t<-1, SAMPLER, T, NC, SHAPE>(img, map, stream);
-}
-
-template <typename T, int NC, int SHAPE = 0>
-static hipError_t launch_color_s(const ImageArgs& img, const MapArgs& map, int sampler, hipStream_t stream) {
-  if (sampler == kNearest) return launch_color_n<kNearest, T, NC, SHAPE>(img, map, stream);
-  if constexpr (std::is_same<T, float>::value) {
-    if (sampler == kF64Lerp) return launch_color_n<kF64Lerp, T, NC, SHAPE>(img, map, stream);
+  if constexpr (KIND == kPersp) {                  // no polynomial: one instantiation
+    return launch_color_t<kPersp, 0, SAMPLER, T, NC, SHAPE>(img, map, stream);
+  } else {
+    if (map.nfact <= 5) return launch_color_t<KIND, 5, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 5), stream);
+    if (map.nfact <= 10) return launch_color_t<KIND, 10, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 10), stream);
+    return launch_color_t<KIND, -1, SAMPLER, T, NC, SHAPE>(img, map, stream);
   }
-  return launch_color_n<kScipy, T, NC, SHAPE>(img, map, stream);
 }
 
-template <typename T>
+template <int KIND, typename T, int NC, int SHAPE = 0>
+static hipError_t launch_color_s(const ImageArgs& img, const MapArgs& map, int sampler, hipStream_t stream) {
+  if (sampler == kNearest) return launch_color_n<KIND, kNearest, T, NC, SHAPE>(img, map, stream);
+  if constexpr (std::is_same<T, float>::value) {
+    if (sampler == kF64Lerp) return launch_color_n<KIND, kF64Lerp, T, NC, SHAPE>(img, map, stream);
+  }
+  return launch_color_n<KIND, kScipy, T, NC, SHAPE>(img, map, stream);
+}
+
+template <int KIND, typename T>
 static hipError_t launch_color_c(const ImageArgs& img, const MapArgs& map, int channels, int sampler, hipStream_t stream) {
-  if (channels == 3) return launch_color_s<T, 3>(img, map, sampler, stream);
-  return launch_color_s<T, 4>(img, map, sampler, stream);
+  if (channels == 3) return launch_color_s<KIND, T, 3>(img, map, sampler, stream);
+  return launch_color_s<KIND, T, 4>(img, map, sampler, stream);
+}
+template <typename T>
+static hipError_t launch_color_k(MapKind kind, const ImageArgs& img, const MapArgs& map, int channels, int sampler, hipStream_t stream) {
+  if (kind == kPersp) return launch_color_c<kPersp, T>(img, map, channels, sampler, stream);
+  if (kind == kFused) return launch_color_c<kFused, T>(img, map, channels, sampler, stream);
+  return launch_color_c<kRadial, T>(img, map, channels, sampler, stream);
 }
 // single-plane frames of the 4- and 8-byte element types the single-plane kernel (remap_wg_kernel: float32, 8- / 16-bit) does not take
 template <typename T>
 static hipError_t launch_plane(const ImageArgs& img, const MapArgs& map, int sampler, hipStream_t stream) {
-  return launch_color_s<T, 1>(img, map, sampler, stream);
+  return launch_color_s<kRadial, T, 1>(img, map, sampler, stream);
 }
 
-// Interleaved pixels of 3 or 4 channels, float32 / uint8 / uint16 -- or ONE channel of float64 / int32 / uint32 (the single-plane
-// frames remap_wg_kernel has no instantiation for) --, dense (pixel stride = channels), radial map under the level-2
-// certificate, orders 0 / 1.  *taken = false: the call does not qualify and the one-thread-per-pixel kernels must serve it.
-hipError_t launch_color(const ImageArgs& img_in, const MapArgs& map, int channels, int dtype, int sampler, const LaunchOpts& opts, hipStream_t stream,
-                        bool* taken) {
+// Interleaved pixels of 3 or 4 channels, float32 / uint8 / uint16, under the radial map, the homography or the fused map -- or ONE
+// channel of float64 / int32 / uint32 under the radial map (the single-plane frames remap_wg_kernel has no instantiation for) --,
+// dense (pixel stride = channels), level-2 certificate of the map's kind, orders 0 / 1.  *taken = false: the call does not qualify
+// and the one-thread-per-pixel kernels must serve it.
+hipError_t launch_color(MapKind kind, const ImageArgs& img_in, const MapArgs& map, int channels, int dtype, int sampler, const LaunchOpts& opts,
+                        hipStream_t stream, bool* taken) {
   *taken = false;
+  if (kind != kRadial && kind != kPersp && kind != kFused) return hipSuccess;
+  const bool radial = kind == kRadial;
   if (!opts.wg_box || !opts.lds_gather || opts.coef_lds || opts.xcd_remap == 1) return hipSuccess;
-  if (!(map.tile_dev_ok >= 2 || (channels == 1 && dtype == kF32 && img_in.tile_rows == 64 && map.tall_ok))) return hipSuccess;
+  if (!(map.tile_dev_ok >= 2 || (radial && channels == 1 && dtype == kF32 && img_in.tile_rows == 64 && map.tall_ok))) return hipSuccess;
   if (channels == 1 && dtype == kF32 && img_in.tile_rows == 128 && map.tile_dev_ok < 2) return hipSuccess;
   const bool colour = (channels == 3 || channels == 4) && (dtype == kF32 || dtype == kU8 || dtype == kU16);
   // (float32 single planes: only the 64 x 32 tile shape for sheared maps, img.tile_rows = 64 -- launch_plane_tall below; the
   // 128-wide shapes of float32 belong to remap_wg_kernel)
-  const bool tall = channels == 1 && dtype == kF32 && img_in.tile_rows == 64;
-  const bool flat = channels == 1 && dtype == kF32 && img_in.tile_rows == 128;      // (A/B only: option tall_tiles = 2)
-  const bool plane = channels == 1 && (dtype == kF64 || dtype == kI32 || dtype == kU32 || tall || flat);
+  const bool tall = radial && channels == 1 && dtype == kF32 && img_in.tile_rows == 64;
+  const bool flat = radial && channels == 1 && dtype == kF32 && img_in.tile_rows == 128;      // (A/B only: option tall_tiles = 2)
+  const bool plane = radial && channels == 1 && (dtype == kF64 || dtype == kI32 || dtype == kU32 || tall || flat);
   if (!colour && !plane) return hipSuccess;
   if (sampler != kNearest && sampler != kScipy && !(sampler == kF64Lerp && dtype == kF32)) return hipSuccess;
   const int es = elem_size(dtype);
@@ -454,12 +522,12 @@ hipError_t launch_color(const ImageArgs& img_in, const MapArgs& map, int channel
       (int64_t)img.src_stride * es >= (1ll << 31) || img.H >= (1 << 24) || (int64_t)img.W * channels * es >= (1ll << 28))
     return hipSuccess;
   *taken = true;
-  if (tall) return launch_color_s<float, 1, 1>(img, map, sampler, stream);
-  if (flat) return launch_color_s<float, 1, 0>(img, map, sampler, stream);
+  if (tall) return launch_color_s<kRadial, float, 1, 1>(img, map, sampler, stream);
+  if (flat) return launch_color_s<kRadial, float, 1, 0>(img, map, sampler, stream);
   switch (dtype) {
-    case kF32: return launch_color_c<float>(img, map, channels, sampler, stream);
-    case kU8: return launch_color_c<uint8_t>(img, map, channels, sampler, stream);
-    case kU16: return launch_color_c<uint16_t>(img, map, channels, sampler, stream);
+    case kF32: return launch_color_k<float>(kind, img, map, channels, sampler, stream);
+    case kU8: return launch_color_k<uint8_t>(kind, img, map, channels, sampler, stream);
+    case kU16: return launch_color_k<uint16_t>(kind, img, map, channels, sampler, stream);
     case kF64: return launch_plane<double>(img, map, sampler, stream);
     case kI32: return launch_plane<int32_t>(img, map, sampler, stream);
     default: return launch_plane<uint32_t>(img, map, sampler, stream);

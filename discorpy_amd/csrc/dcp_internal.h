@@ -247,11 +247,11 @@ struct ForwardArgs {
   int32_t esize;
 };
 hipError_t launch_forward(const ForwardArgs& a, const MapArgs& map, hipStream_t stream);
-// interleaved (H, W, C) image, radial map, orders 0 / 1; src_cstride = elements between pixels
-hipError_t launch_typed_channels(const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
-// color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, certified radial map);
-// img as for launch_wg_typed with src_col_stride = channels; *taken = false: does not qualify, use launch_typed_channels
-hipError_t launch_color(const ImageArgs& img, const MapArgs& map, int channels, int dtype, int sampler, const LaunchOpts& opts, hipStream_t stream,
-                        bool* taken);
+// interleaved (H, W, C) image, radial / perspective / fused map, orders 0 / 1; src_cstride = elements between pixels
+hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
+// color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, level-2 certificate of
+// the map's kind); img as for launch_wg_typed with src_col_stride = channels; *taken = false: does not qualify, use launch_typed_channels
+hipError_t launch_color(MapKind kind, const ImageArgs& img, const MapArgs& map, int channels, int dtype, int sampler, const LaunchOpts& opts,
+                        hipStream_t stream, bool* taken);
 
 }  // namespace dcp

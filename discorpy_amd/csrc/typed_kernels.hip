@@ -99,8 +99,9 @@ __global__ void __launch_bounds__(kTypedBlock) typed_image_kernel(const TypedIma
 
 // Interleaved (H, W, C) image, every channel sampled at the SAME coordinate -- what
 // util.unwarp_color_image_backward does channel by channel (discorpy/util/utility.py:327-341): one
-// coordinate evaluation and C blends per pixel, taps of a pixel's C channels contiguous in memory.
-template <typename T>
+// coordinate evaluation and C blends per pixel, taps of a pixel's C channels contiguous in memory.  KIND: the radial map, or the
+// homography / the fused map, where the reference's demos loop correct_perspective_image over the channels (demo_07.py:25,60).
+template <typename T, int KIND>
 __global__ void __launch_bounds__(kTypedBlock) typed_channels_kernel(const TypedImageArgs a, const MapArgs map, int C) {
   const int x = blockIdx.x * kTypedBlock + (int)threadIdx.x;
   const int yl = blockIdx.y + blockIdx.z * 65535;          // row inside the band [y0, y0 + rows)
@@ -109,7 +110,7 @@ __global__ void __launch_bounds__(kTypedBlock) typed_channels_kernel(const Typed
   const int64_t i = (int64_t)yl * a.W + x;
   const float wmaxf = (float)(a.W - 1), hmaxf = (float)(a.H - 1);
   double xd, yd;
-  pixel_coord<kRadial>(map, (double)x, (double)y, wmaxf, hmaxf, &xd, &yd);
+  pixel_coord<KIND>(map, (double)x, (double)y, wmaxf, hmaxf, &xd, &yd);
   const double xc = (double)round_clip_f32(xd, wmaxf), yc = (double)round_clip_f32(yd, hmaxf);
   const T* src = (const T*)a.src;
   T* dst = (T*)a.dst + i * C;
@@ -371,14 +372,23 @@ hipError_t launch_typed_image(MapKind kind, const TypedImageArgs& a, const MapAr
 }
 
 template <typename T>
-static hipError_t launch_channels_t(const TypedImageArgs& a, const MapArgs& map, int channels, hipStream_t stream) {
-  hipLaunchKernelGGL((typed_channels_kernel<T>), image_grid(a.rows, a.W), dim3(kTypedBlock), 0, stream, a, map, channels);
+static hipError_t launch_channels_t(MapKind kind, const TypedImageArgs& a, const MapArgs& map, int channels, hipStream_t stream) {
+  const dim3 grid = image_grid(a.rows, a.W), block(kTypedBlock);
+  switch (kind) {
+    case kRadial: hipLaunchKernelGGL((typed_channels_kernel<T, kRadial>), grid, block, 0, stream, a, map, channels); break;
+    case kPersp: hipLaunchKernelGGL((typed_channels_kernel<T, kPersp>), grid, block, 0, stream, a, map, channels); break;
+    case kFused: hipLaunchKernelGGL((typed_channels_kernel<T, kFused>), grid, block, 0, stream, a, map, channels); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_typed_channels(const TypedImageArgs& a, const MapArgs& map, int channels, hipStream_t stream) {
-  set_last_kernel_name("typed_channels_kernel (interleaved channels, one thread per pixel)");
-#define DCP_CALL(T) launch_channels_t<T>(a, map, channels, stream)
+hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& a, const MapArgs& map, int channels, hipStream_t stream) {
+  // (the radial map is not named: the name it had before the other maps came)
+  set_last_kernel_name(kind == kPersp   ? "typed_channels_kernel<Persp> (interleaved channels, one thread per pixel)"
+                       : kind == kFused ? "typed_channels_kernel<Fused> (interleaved channels, one thread per pixel)"
+                                        : "typed_channels_kernel (interleaved channels, one thread per pixel)");
+#define DCP_CALL(T) launch_channels_t<T>(kind, a, map, channels, stream)
   DCP_TYPED_DISPATCH(a.dtype, DCP_CALL)
 #undef DCP_CALL
 }

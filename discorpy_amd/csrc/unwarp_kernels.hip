@@ -2235,7 +2235,7 @@ hipError_t launch_image(MapKind kind, const ImageArgs& img_in, const MapArgs& ma
       ImageArgs t = img;
       t.tile_rows = 64;
       bool taken = false;
-      const hipError_t e = launch_color(t, map, 1, kF32, sampler, opts, stream, &taken);
+      const hipError_t e = launch_color(kRadial, t, map, 1, kF32, sampler, opts, stream, &taken);
       if (e != hipSuccess || taken) return e;
     }
     if (pair && round_f32 && !opts.coef_lds && img.lds_gather && img.wg_box && opts.tall_tiles == 2 && map.tile_dev_ok >= 2 && opts.xcd_remap != 1 &&
@@ -2243,7 +2243,7 @@ hipError_t launch_image(MapKind kind, const ImageArgs& img_in, const MapArgs& ma
       ImageArgs t = img;
       t.tile_rows = 128;
       bool taken = false;
-      const hipError_t e = launch_color(t, map, 1, kF32, sampler, opts, stream, &taken);
+      const hipError_t e = launch_color(kRadial, t, map, 1, kF32, sampler, opts, stream, &taken);
       if (e != hipSuccess || taken) return e;
     }
     if (pair && round_f32 && !opts.coef_lds) {

@@ -5,6 +5,10 @@
 unwarp of every channel at the SAME float32 coordinates -- one launch on the interleaved image for
 orders 0 / 1, plane by plane through :mod:`discorpy_amd.post.postprocessing` otherwise.
 
+``correct_perspective_color_image`` and ``unwarp_perspective_fused_color_image`` do the same for the homography and for the
+one-pass perspective -> radial map: what the reference's demos write as a loop of ``post.correct_perspective_image`` over
+``mat[:, :, i]`` (``examples/readthedocs_demo/demo_07.py:25,60``; ``demo_05.py:127,147``) is one call on the interleaved image.
+
 ``find_point_to_point`` is the closed-form point mapping of ``utility.py:192-230`` (host, NumPy);
 ``transform_coef_backward_and_forward`` the small least-squares model reversal ``pad=True`` needs
 (``proc/processing.py:615-674``; host, NumPy -- the north star keeps the one-off fits on the CPU).
@@ -13,7 +17,8 @@ import numpy as np
 
 from ..post import postprocessing as _pp
 
-__all__ = ["unwarp_color_image_backward", "find_point_to_point", "transform_coef_backward_and_forward"]
+__all__ = ["unwarp_color_image_backward", "find_point_to_point", "transform_coef_backward_and_forward",
+           "correct_perspective_color_image", "unwarp_perspective_fused_color_image"]
 
 
 def find_point_to_point(points, xcenter, ycenter, list_fact, output_order="xy"):
@@ -114,24 +119,161 @@ def _pad_device(t, pad_width, mode):
     return t
 
 
+def _interleaved_image(mat):
+    """The (H, W, C) image as the interleaved-channel entry points address it -- unit channel stride, pixel stride >= C, rows that
+    do not overlap --, after ONE contiguous copy where the layout is another; returns (image, row stride, pixel stride)."""
+    img = _pp._Image(mat, 3)
+    h, w, c = img.shape
+    rs, ps, cs = img.strides
+    if cs != 1 or ps < c or (h > 1 and rs < (w - 1) * ps + c):
+        img = _pp._Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 3)
+        rs, ps, cs = img.strides
+    return img, rs, ps
+
+
 def _unwarp_interleaved(mat_pad, xcenter, ycenter, list_fact, order, blend=None):
     """(H, W, C) interleaved image in one launch of dcp_unwarp_color_image: one coordinate per pixel, C blends in the
     arithmetic `blend` names (the default of unwarp_image_backward when None; integer pixels always in scipy's exact order),
     no per-channel planes on the host.  3 / 4 channels of float32 / uint8 / uint16 under a certified calibration run
     remap_wg_color_kernel (the source box of a tile staged in LDS once for all channels)."""
     F = _pp.F
-    img = _pp._Image(mat_pad, 3)
+    img, rs, ps = _interleaved_image(mat_pad)
     h, w, c = img.shape
-    rs, ps, cs = img.strides
-    if cs != 1 or ps < c or (h > 1 and rs < (w - 1) * ps + c):
-        img = _pp._Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 3)
-        rs, ps, cs = img.strides
     fa, nf = F.fact_array(_pp._coefs(list_fact, "list_fact"))
     out, optr = img.empty((h, w, c))
     F.require_device()
     F.check(F.lib().dcp_unwarp_color_image(img.ptr, optr, img.code, h, w, c, rs, ps, float(xcenter), float(ycenter),
                                            fa, nf, order, _pp._blend_code(blend, img.mem == F.MEM_HOST), img.mem, img.device, img.stream))
     return out
+
+
+def _homography_interleaved(mat, radial, list_coef, order, blend=None):
+    """As _unwarp_interleaved under the homography `list_coef` (dcp_perspective_color_image) or, with radial = (xcenter, ycenter,
+    list_fact), under the one-pass perspective -> radial map (dcp_unwarp_fused_color_image)."""
+    F = _pp.F
+    img, rs, ps = _interleaved_image(mat)
+    h, w, c = img.shape
+    ca, _ = F.fact_array(_pp._coefs(list_coef, "list_coef"))
+    bcode = _pp._blend_code(blend, img.mem == F.MEM_HOST)
+    if radial is not None:
+        fa, nf = F.fact_array(_pp._coefs(radial[2], "list_fact"))
+    out, optr = img.empty((h, w, c))
+    F.require_device()
+    if radial is None:
+        F.check(F.lib().dcp_perspective_color_image(img.ptr, optr, img.code, h, w, c, rs, ps, ca, order, bcode, img.mem, img.device,
+                                                    img.stream))
+    else:
+        F.check(F.lib().dcp_unwarp_fused_color_image(img.ptr, optr, img.code, h, w, c, rs, ps, float(radial[0]), float(radial[1]), fa, nf,
+                                                     ca, order, bcode, img.mem, img.device, img.stream))
+    return out
+
+
+def _one_launch(order, blend, channels):
+    """Do the interleaved-channel entry points take this call?  Orders 0 / 1, scipy's blend or its one-ulp factorisation
+    (names are case-insensitive), 1 to 64 channels."""
+    return order <= 1 and (blend is None or str(blend).lower() in ("scipy", "exact", "f64lerp", "f64")) and 1 <= channels <= 64
+
+
+def _plane_by_plane(mat, plane_call):
+    """The reference's loop over mat[:, :, i] (demo_07.py:25,60): every channel through the single-plane function."""
+    is_torch = _pp._is_torch(mat)
+    if mat.shape[2] == 0:
+        return mat.clone() if is_torch else np.array(mat)
+    planes = [plane_call(mat[:, :, i]) for i in range(mat.shape[2])]
+    if is_torch:
+        import torch
+        return torch.stack(planes, dim=2)
+    return np.stack([np.asarray(p) for p in planes], axis=2)
+
+
+def _complex_split(mat, call):
+    """scipy interpolates a complex array as its real and imaginary parts: `call` on each, joined; None for real data."""
+    parts = _pp._complex_parts(mat)
+    if parts is None:
+        return None
+    dense = (lambda t: t.contiguous()) if _pp._is_torch(mat) else np.ascontiguousarray
+    return parts[2](call(dense(parts[0])), call(dense(parts[1])))
+
+
+def correct_perspective_color_image(mat, list_coef, order=1, mode="reflect", map_index=None, *, blend=None):
+    """
+    Apply perspective correction to a colour image: ``post.correct_perspective_image`` (reference
+    ``postprocessing.py:462-492``) on every channel of an interleaved image, as the loop of
+    ``examples/readthedocs_demo/demo_07.py:25,60`` does, at ONE evaluation of the coordinates of ``:444-459``.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D/3D array (H, W) or (H, W, C); NumPy array or ROCm torch tensor.  A 2D array is handed to
+        ``post.correct_perspective_image``.
+    list_coef : list of floats
+        Coefficients of the backward-mapping matrix (c1..c8, (x, y) convention).
+    order : int, optional.
+        The order of the spline interpolation (0..5); orders 2..5 go plane by plane.
+    mode : str, optional
+        Boundary mode of scipy's spline interpolation; inert for order <= 1.
+    map_index : array_like
+        Indices for mapping, (ycoords, xcoords) with height*width points: every plane is remapped at them.
+
+    Returns
+    -------
+    array_like
+        Corrected image: the input's shape, element type and container.
+    """
+    if len(list_coef) != 8:
+        raise ValueError("!!! Eight coefficients are required !!!")
+    if len(mat.shape) == 2:
+        return _pp.correct_perspective_image(mat, list_coef, order=order, mode=mode, map_index=map_index, blend=blend)
+    order = _pp._check_order_mode(order, mode)
+    res = _complex_split(mat, lambda part: correct_perspective_color_image(part, list_coef, order, mode, map_index, blend=blend))
+    if res is not None:
+        return res
+    if map_index is None and _one_launch(order, blend, mat.shape[2]):
+        return _homography_interleaved(mat, None, list_coef, order, blend)
+    return _plane_by_plane(mat, lambda plane: _pp.correct_perspective_image(plane, list_coef, order=order, mode=mode,
+                                                                            map_index=map_index, blend=blend))
+
+
+def unwarp_perspective_fused_color_image(mat, xcenter, ycenter, list_fact, list_coef, order=1, mode="reflect", *, blend=None):
+    """
+    Perspective and radial correction of a colour image in ONE resampling: ``post.unwarp_perspective_fused`` on every
+    channel of an interleaved image at one evaluation of the composed coordinates (the reference resamples twice,
+    ``examples/readthedocs_demo/demo_05.py:127,147``; see there for the definition of the one-pass map).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D/3D array (H, W) or (H, W, C); NumPy array or ROCm torch tensor.  A 2D array is handed to
+        ``post.unwarp_perspective_fused``.
+    xcenter, ycenter : float
+        Center of distortion.
+    list_fact : list of float
+        Polynomial coefficients of the backward radial model.
+    list_coef : list of floats
+        Coefficients of the backward-mapping matrix (c1..c8, (x, y) convention).
+    order : int, optional.
+        The order of the spline interpolation (0..5); orders 2..5 go plane by plane.
+    mode : str, optional
+        Boundary mode of scipy's spline interpolation; inert for order <= 1.
+
+    Returns
+    -------
+    array_like
+        Corrected image: the input's shape, element type and container.
+    """
+    if len(list_coef) != 8:
+        raise ValueError("!!! Eight coefficients are required !!!")
+    if len(mat.shape) == 2:
+        return _pp.unwarp_perspective_fused(mat, xcenter, ycenter, list_fact, list_coef, order=order, mode=mode, blend=blend)
+    order = _pp._check_order_mode(order, mode)
+    res = _complex_split(mat, lambda part: unwarp_perspective_fused_color_image(part, xcenter, ycenter, list_fact, list_coef, order,
+                                                                                mode, blend=blend))
+    if res is not None:
+        return res
+    if _one_launch(order, blend, mat.shape[2]):
+        return _homography_interleaved(mat, (xcenter, ycenter, list_fact), list_coef, order, blend)
+    return _plane_by_plane(mat, lambda plane: _pp.unwarp_perspective_fused(plane, xcenter, ycenter, list_fact, list_coef, order=order,
+                                                                           mode=mode, blend=blend))
 
 
 def unwarp_color_image_backward(mat, xcenter, ycenter, list_fact, order=1, mode="reflect", pad=False,

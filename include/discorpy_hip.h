@@ -349,6 +349,20 @@ int dcp_unwarp_image_channels(const void* src, void* dst, int dtype, int64_t hei
                               int64_t src_row_stride, int64_t src_pixel_stride, double xcenter, double ycenter,
                               const double* list_fact, int nfact, int order, int mem_kind, int device, void* stream);
 
+/* Interleaved pixels under the homography, and under the one-pass perspective -> radial map.  The reference's demos loop
+ * post.correct_perspective_image(mat[:, :, i], list_coef) over the channels of a colour photograph
+ * (examples/readthedocs_demo/demo_07.py:25,60; demo_05.py:127,147 corrects the radial distortion and then the perspective of the
+ * same image): per channel the coordinates of discorpy/post/postprocessing.py:444-459 and the map_coordinates call of :462-492.
+ * Here one coordinate evaluation and `channels` blends per pixel, orders 0 / 1; arguments, blend_mode rule and kernel choice as
+ * dcp_unwarp_color_image (the staged kernel under the level-2 certificate of the map's kind, else one thread per pixel -- the same
+ * values either way, and the same as dcp_perspective_image_f32 / _typed and dcp_unwarp_fused_f32 / _typed give per plane). */
+int dcp_perspective_color_image(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                int64_t src_pixel_stride, const double* list_coef, int order, int blend_mode, int mem_kind, int device,
+                                void* stream);
+int dcp_unwarp_fused_color_image(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                 int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
+                                 const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream);
+
 /* ---- out-of-core stacks ----
  * The reference never touches more of a projection than mat3D[i, yd_min:yd_max, :]
  * (discorpy/post/postprocessing.py:221-228, 295-301), which is what lets it run on an HDF5 dataset

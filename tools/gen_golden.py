@@ -634,4 +634,44 @@ def g23():
 
 
 g23()
+
+
+# G24: a colour photograph under a homography, as the reference's demos do it: examples/readthedocs_demo/demo_07.py:25,60 loops
+# post.correct_perspective_image(mat[:, :, i], list_coef) over the channels (orders 1 and 3 there; order 0 added); and the one-pass
+# perspective -> radial map per channel, formed exactly as G7 forms fused_out (one map_coordinates at the composed float32 planes).
+# G10's frame (40 x 56 x 3), float32 and uint8 pixels, configs.CFG3_COEF rescaled as G7 rescales it.  Arrays only.
+def g24():
+    h, w, nc = 40, 56, 3
+    seed = 2424
+    rng = np.random.default_rng(seed)
+    images = {"f32": rng.random((h, w, nc), dtype=np.float32) * np.float32(255.0),
+              "u8": rng.integers(0, 256, (h, w, nc), dtype=np.uint8)}
+    s = 4096 / w
+    c = list(configs.CFG3_COEF)
+    coef = [c[0], c[1], c[2] / s, c[3], c[4], c[5] / s, c[6] * s, c[7] * s]
+    xc, yc, fact = configs.rescale_model(w)
+    yp, xp = post._generate_perspective_map(images["f32"][:, :, 0], coef)
+    xu = np.float64(xp.reshape(h, w)) - xc
+    yu = np.float64(yp.reshape(h, w)) - yc
+    ru = np.sqrt(xu ** 2 + yu ** 2)
+    fm = np.sum(np.asarray([f * ru ** i for i, f in enumerate(fact)]), axis=0)
+    xd = np.float32(np.clip(xc + fm * xu, 0, w - 1))
+    yd = np.float32(np.clip(yc + fm * yu, 0, h - 1))
+    out = dict(seed=np.int64(seed), shape=np.array([h, w, nc]), xcenter=f64(xc), ycenter=f64(yc), list_fact=f64(fact), list_coef=f64(coef),
+               yd=yd, xd=xd)
+    for tag, rgb in images.items():
+        out["rgb_" + tag] = rgb
+        for order in (1, 0, 3):
+            planes = []
+            for i in range(nc):                      # demo_07.py:25,60
+                planes.append(post.correct_perspective_image(rgb[:, :, i], coef, order=order))
+            out["persp_%s_o%d" % (tag, order)] = np.stack(planes, axis=2)
+            out["fused_%s_o%d" % (tag, order)] = np.stack(
+                [map_coordinates(rgb[:, :, i], (yd.reshape(-1, 1), xd.reshape(-1, 1)), order=order, mode="reflect").reshape(h, w)
+                 for i in range(nc)], axis=2)
+            assert out["persp_%s_o%d" % (tag, order)].dtype == rgb.dtype and out["fused_%s_o%d" % (tag, order)].dtype == rgb.dtype
+    save("g24_colour_homography40x56x3", **out)
+
+
+g24()
 print("done")

@@ -4,7 +4,12 @@ remap_wg_color_kernel, through the one-thread-per-pixel kernel (option wg_box=0)
 remap_wg_kernel on planar copies.  us per image, HIP events after 300 ms of the same launches; a ring of images larger than the
 256 MB Infinity Cache.
 
-    python tools/time_color.py [--size 4096] [--ring 6] [--reps 60] [--cases f32x3,f32x4,u8x3,u16x3]
+--map perspective / fused: the interleaved image under the homography (dcp_perspective_color_image) or the one-pass perspective ->
+radial map (dcp_unwarp_fused_color_image) against NC single-plane calls on planes that are already split and dense (the two
+transposes a user of the single-plane functions also pays are not charged to them), the two ALTERNATING in one run: --rounds
+rounds of --reps launches each, median and range per side, the core clock under the colour kernel.
+
+    python tools/time_color.py [--map radial|perspective|fused] [--size 4096] [--ring 6] [--reps 60] [--rounds 5] [--cases f32x3,f32x4,u8x3,u16x3]
 """
 import argparse
 import os
@@ -18,8 +23,83 @@ from discorpy_amd import _ffi as F  # noqa: E402
 from discorpy_amd import configs  # noqa: E402
 
 
+def ab_homography(a, L, dev):
+    """--map perspective / fused: colour call against NC single-plane calls, alternating."""
+    H = W = a.size
+    s = a.size / 4096.0
+    cfg = configs.cfg3()
+    c = cfg["list_coef"]
+    ca, _ = F.fact_array([c[0], c[1], c[2] * s, c[3], c[4], c[5] * s, c[6] / s, c[7] / s])     # (as tools/gen_golden.py rescales it)
+    fa, nf = F.fact_array([v * s ** -i for i, v in enumerate(cfg["list_fact"])])
+    xc, yc = cfg["xcenter"] * s, cfg["ycenter"] * s
+    fused = a.map == "fused"
+    dt = {"f32": ("float32", 0), "u8": ("uint8", 2), "u16": ("uint16", 4)}
+    rng = np.random.default_rng(3)
+    for case in a.cases.split(","):
+        tname, nc = case.split("x")
+        nc = int(nc)
+        if tname not in dt or nc not in (3, 4):
+            continue
+        npdt, code = dt[tname]
+        es = np.dtype(npdt).itemsize
+        nbytes = H * W * nc * es
+        ring = max(2, min(a.ring, int(3e9 // (4 * nbytes)) or 2))
+        img = (rng.random((H, W, nc), dtype=np.float32) * (255 if tname != "f32" else 1)).astype(npdt)
+        srcs = [F.DeviceBuffer(nbytes, dev).upload(img) for _ in range(ring)]
+        dsts = [F.DeviceBuffer(nbytes, dev) for _ in range(ring)]
+        planes = [F.DeviceBuffer(H * W * es, dev).upload(np.ascontiguousarray(img[:, :, k % nc])) for k in range(nc * ring)]
+        outs = [F.DeviceBuffer(H * W * es, dev) for _ in range(nc * ring)]
+        for name, order, blend in (("f64lerp", 1, F.BLEND_F64LERP), ("scipy", 1, F.BLEND_SCIPY), ("nearest", 0, F.BLEND_SCIPY)):
+            if tname != "f32" and name == "f64lerp":
+                continue
+
+            def colour(i):
+                sp, dp = srcs[i % ring].ptr, dsts[i % ring].ptr
+                if fused:
+                    F.check(L.dcp_unwarp_fused_color_image(sp, dp, code, H, W, nc, W * nc, nc, xc, yc, fa, nf, ca, order, blend, F.MEM_DEVICE, dev, None))
+                else:
+                    F.check(L.dcp_perspective_color_image(sp, dp, code, H, W, nc, W * nc, nc, ca, order, blend, F.MEM_DEVICE, dev, None))
+
+            def planar(i):
+                for k in range(nc):
+                    j = (i % ring) * nc + k
+                    sp, dp = planes[j].ptr, outs[j].ptr
+                    if tname == "f32" and fused:
+                        F.check(L.dcp_unwarp_fused_f32(sp, dp, H, W, W, 1, xc, yc, fa, nf, ca, order, blend, F.MEM_DEVICE, dev, None))
+                    elif tname == "f32":
+                        F.check(L.dcp_perspective_image_f32(sp, dp, H, W, W, 1, ca, order, blend, F.MEM_DEVICE, dev, None))
+                    elif fused:
+                        F.check(L.dcp_unwarp_fused_typed(sp, dp, code, H, W, W, 1, xc, yc, fa, nf, ca, order, 0, F.MEM_DEVICE, dev, None))
+                    else:
+                        F.check(L.dcp_perspective_image_typed(sp, dp, code, H, W, W, 1, ca, order, 0, F.MEM_DEVICE, dev, None))
+
+            tc, tp = [], []
+            for r in range(a.rounds):
+                tc.append(bench.timed_launches(colour, a.reps, dev, settle_ms=300.0 if r == 0 else 60.0))
+                kc = F.last_kernel()
+                tp.append(bench.timed_launches(planar, a.reps, dev, settle_ms=60.0))
+                kp = F.last_kernel()
+            mc, mp = float(np.median(tc)), float(np.median(tp))
+            print("%-11s %-6s %-8s colour %8.2f us [%.2f .. %.2f]  %.3f of 8 TB/s (%d B/px)  %s" % (
+                a.map, case, name, mc, min(tc), max(tc), 2 * nbytes / (mc * 1e-6) / 8e12, 2 * nc * es, kc), flush=True)
+            print("%-11s %-6s %-8s %d planes %7.2f us [%.2f .. %.2f]  colour / planes = %.3f  %s" % (
+                a.map, case, name, nc, mp, min(tp), max(tp), mc / mp, kp), flush=True)
+            if name != "nearest" and not a.no_generic:
+                F.set_option("x_wg_box", 0)
+                tg = bench.timed_launches(colour, max(4, a.reps // 4), dev, settle_ms=100.0)
+                F.set_option("x_wg_box", 1)
+                print("%-11s %-6s %-8s one thread per pixel: %.2f us" % (a.map, case, name, tg), flush=True)
+            if name in ("f64lerp", "scipy") and (tname == "f32") == (name == "f64lerp"):
+                clk = bench.clocks_under_load(lambda: colour(0), lambda: F.check(L.dcp_stream_synchronize(dev, None)))
+                print("%-11s %-6s clock under the colour kernel: %s" % (a.map, case, clk), flush=True)
+        for b in srcs + dsts + planes + outs:
+            b.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--map", choices=("radial", "perspective", "fused"), default="radial")
+    ap.add_argument("--rounds", type=int, default=5, help="--map perspective / fused: alternations of the two sides")
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--ring", type=int, default=6)
     ap.add_argument("--reps", type=int, default=60)
@@ -29,6 +109,8 @@ def main():
     L = F.lib()
     F.require_device()
     dev = -1
+    if a.map != "radial":
+        return ab_homography(a, L, dev)
     cfg = configs.cfg2()
     s = a.size / 4096.0
     fact = [c * s ** -i for i, c in enumerate(cfg["list_fact"])]
