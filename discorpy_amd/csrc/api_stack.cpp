@@ -455,6 +455,82 @@ int dcp_unwarp_stack_rows_centres_f32(const float* vol, float* out, int64_t dept
   return DCP_OK;
 }
 
+int dcp_remap_frames_typed(const void* src, void* dst, int dtype, int map_kind, int64_t nframes, int64_t height, int64_t width,
+                           int64_t frame_stride, int64_t row_stride, double xcenter, double ycenter, const double* list_fact,
+                           int nfact, const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream) {
+  int rc, sampler = dcp::kScipy;
+  bool host = false;
+  if (dtype < 0 || dtype >= dcp::kNumElemTypes) return fail(DCP_ERR_INVALID_ARG, "unknown element type %d", dtype);
+  if (map_kind == DCP_MAP_RADIAL)
+    return fail(DCP_ERR_INVALID_ARG, "dcp_remap_frames_typed takes DCP_MAP_PERSPECTIVE or DCP_MAP_FUSED: frames under the radial map alone are the "
+                "projections of a stack, dcp_unwarp_stack_rows_f32 / dcp_unwarp_stack_rows_typed (row_start = 0, nrows = height, coord_round_f32 = 2)");
+  if (map_kind != DCP_MAP_PERSPECTIVE && map_kind != DCP_MAP_FUSED) return fail(DCP_ERR_INVALID_ARG, "unknown map_kind %d", map_kind);
+  if ((rc = mem_kind_of(mem_kind, &host)) != DCP_OK) return rc;
+  if (nframes < 0) return fail(DCP_ERR_INVALID_ARG, "nframes < 0");
+  if (height <= 0 || width <= 0) return fail(DCP_ERR_INVALID_ARG, "frames must be non-empty (got %lld x %lld)", (long long)height, (long long)width);
+  if (row_stride < width) return fail(DCP_ERR_INVALID_ARG, "row stride %lld overlaps rows of width %lld", (long long)row_stride, (long long)width);
+  if (nframes > 1 && frame_stride < (height - 1) * row_stride + width)
+    return fail(DCP_ERR_INVALID_ARG, "frame stride %lld overlaps frames of %lld rows, %lld elements apart", (long long)frame_stride, (long long)height,
+                (long long)row_stride);
+  if (order < 0 || order > 1) return fail(DCP_ERR_INVALID_ARG, "order %d outside [0, 1] (the spline orders go frame by frame: dcp_*_image_typed)", order);
+  if (nfact < 0 || nfact > dcp::kMaxFact)
+    return fail(DCP_ERR_INVALID_ARG, "nfact = %d outside [0, %d] (DCP_MAX_FACT is a limit of this library, not of the reference)", nfact, dcp::kMaxFact);
+  const dcp::MapKind kind = (dcp::MapKind)map_kind;
+  const bool fused = kind == dcp::kFused;
+  if (!list_coef) return fail(DCP_ERR_INVALID_ARG, "null homography pointer");
+  if (fused && nfact > 0 && !list_fact) return fail(DCP_ERR_INVALID_ARG, "null coefficient pointer");
+  if (dtype == dcp::kF32 && (rc = sampler_of(order, blend_mode, &sampler)) != DCP_OK) return rc;
+  if (nframes == 0) return DCP_OK;
+  if (!src || !dst) return fail(DCP_ERR_INVALID_ARG, "null frame pointer");
+  if (nframes > 2147483647LL) return fail(DCP_ERR_UNSUPPORTED, "too many frames");
+  const int64_t esz = dcp::elem_size(dtype);
+  // One launch: device memory, order 1, float32 / uint8 / uint16, the map certified at level 2 for its kind (which a tame homography
+  // is part of), a frame within 32-bit byte offsets -- and a launch large enough for stack_wg_kernel (its launcher decides).
+  const double ext = (double)((height - 1) * row_stride + width) * (double)esz;
+  if (!host && order == 1 && (dtype == dcp::kF32 || dtype == dcp::kU8 || dtype == dcp::kU16) && height >= 2 && height <= 65535 && width >= 2 &&
+      ext < 4294900000.0 && g_tile_cert.load() && (!fused || g_fused_wg.load())) {
+    dcp::MapArgs map;
+    if ((rc = fill_map(&map, fused ? xcenter : 0.0, fused ? ycenter : 0.0, fused ? list_fact : nullptr, fused ? nfact : 0, list_coef)) != DCP_OK) return rc;
+    map.fast_div = homography_is_tame(list_coef, height, width);
+    map.tile_dev_ok = map.fast_div ? tile_deviation_certified(kind, map, height, width) : 0;
+    if (map.tile_dev_ok >= 2) {
+      DeviceScope scope(device);
+      if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
+      dcp::StackArgs st;
+      memset(&st, 0, sizeof(st));
+      st.D = (int32_t)nframes;
+      st.H = (int32_t)height;
+      st.W = (int32_t)width;
+      st.row_start = 0.0;
+      st.nrows = (int32_t)height;
+      st.vol = (const float*)src;
+      st.out = (float*)dst;
+      st.proj_stride = frame_stride;
+      st.row_stride = (int32_t)row_stride;
+      st.proj_bytes = (uint32_t)ext;
+      bool taken = false;
+      DCP_HIP(dcp::launch_stack_wg_frames(kind, st, map, dtype, sampler, current_opts(), (hipStream_t)stream, &taken));
+      if (taken) return DCP_OK;
+    }
+  }
+  // Everything else: the single-frame call on every frame, on the same stream -- the single call's bits by construction
+  for (int64_t i = 0; i < nframes; ++i) {
+    const char* s = (const char*)src + (size_t)i * (size_t)frame_stride * (size_t)esz;
+    char* d = (char*)dst + (size_t)i * (size_t)height * (size_t)width * (size_t)esz;
+    if (dtype == dcp::kF32)
+      rc = fused ? dcp_unwarp_fused_f32((const float*)s, (float*)d, height, width, row_stride, 1, xcenter, ycenter, list_fact, nfact, list_coef, order,
+                                        blend_mode, mem_kind, device, stream)
+                 : dcp_perspective_image_f32((const float*)s, (float*)d, height, width, row_stride, 1, list_coef, order, blend_mode, mem_kind, device,
+                                             stream);
+    else
+      rc = fused ? dcp_unwarp_fused_typed(s, d, dtype, height, width, row_stride, 1, xcenter, ycenter, list_fact, nfact, list_coef, order, 0, mem_kind,
+                                          device, stream)
+                 : dcp_perspective_image_typed(s, d, dtype, height, width, row_stride, 1, list_coef, order, 0, mem_kind, device, stream);
+    if (rc != DCP_OK) return rc;
+  }
+  return DCP_OK;
+}
+
 int dcp_stack_row_band(int64_t height, int64_t width, double xcenter, double ycenter, const double* list_fact, int nfact,
                        double row_start, int64_t nrows, int64_t* band_start, int64_t* band_rows) {
   int rc;

@@ -176,6 +176,10 @@ hipError_t launch_image_batch(const ImageArgs& img, const BatchFrame* frames, in
 hipError_t launch_wg_typed(MapKind kind, const ImageArgs& img, const MapArgs& map, int order, int dtype, const LaunchOpts& opts,
                            hipStream_t stream, bool* taken);
 hipError_t launch_stack_wg_typed(const StackArgs& st, const MapArgs& map, int dtype, const LaunchOpts& opts, hipStream_t stream, bool* taken);
+// whole frames of one calibration under a homography / the fused map on stack_wg_kernel (float32, uint8, uint16; order 1; level-2
+// certificate of the map's kind); st as for launch_stack_wg_typed with row_start = 0, nrows = H; *taken = false: frame by frame
+hipError_t launch_stack_wg_frames(MapKind kind, const StackArgs& st, const MapArgs& map, int dtype, int sampler, const LaunchOpts& opts,
+                                  hipStream_t stream, bool* taken);
 hipError_t launch_coords(const ImageArgs& img, const CoordArgs& ca, int sampler, hipStream_t stream);
 hipError_t launch_coord_map(MapKind kind, const ImageArgs& img, const MapArgs& map, float* ymap, float* xmap,
                             hipStream_t stream);

@@ -719,6 +719,32 @@ __device__ __forceinline__ void wg_corner_tap(const ImageArgs& img, const MapArg
   *cyi = (int)round_clip_f32(yd, hmaxf);
 }
 
+// The same rule on the corner's output pixel (X, Y) of a W x H frame (wmaxf = W - 1, hmaxf = H - 1), for stack_wg_kernel under a
+// homography or the fused map (kFused: lanes 0..3 together, corner = lane, as above).  Kept apart from wg_corner_tap so that
+// remap_wg_kernel's code does not move.
+template <int KIND, int NF>
+__device__ __forceinline__ void tile_corner_tap(const MapArgs& map, float wmaxf, float hmaxf, double X, double Y, int corner, int* cxi, int* cyi) {
+  double xd, yd;
+  if constexpr (KIND == kFused) {
+    double px, py;
+    corner_coord<kPersp, NF>(map, X, Y, &px, &py);
+    const float pxf = round_clip_f32(px, wmaxf), pyf = round_clip_f32(py, hmaxf);
+    float qx[4], qy[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      qx[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxf), i));
+      qy[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pyf), i));
+    }
+    const float qx0 = fminf(fminf(qx[0], qx[1]), fminf(qx[2], qx[3])), qx1 = fmaxf(fmaxf(qx[0], qx[1]), fmaxf(qx[2], qx[3]));
+    const float qy0 = fminf(fminf(qy[0], qy[1]), fminf(qy[2], qy[3])), qy1 = fmaxf(fmaxf(qy[0], qy[1]), fmaxf(qy[2], qy[3]));
+    corner_coord<kRadial, NF>(map, (double)((corner & 1) ? qx1 : qx0), (double)((corner & 2) ? qy1 : qy0), &xd, &yd);
+  } else {
+    corner_coord<KIND, NF>(map, X, Y, &xd, &yd);
+  }
+  *cxi = (int)round_clip_f32(xd, wmaxf);
+  *cyi = (int)round_clip_f32(yd, hmaxf);
+}
+
 // T: element type of source and result.  float is the tuned float32 path (any blend).  uint8 / int8 / uint16 / int16
 // (what detectors and cameras deliver) run the same kernel on narrower slab rows -- 16-bit: 20 chunks of 16 bytes =
 // 160 elements, 8-bit: 10 chunks = 160 elements, the box's first column rounded down to a 4-byte boundary -- read their
@@ -1578,7 +1604,10 @@ __global__ void __launch_bounds__(64 * kLdsBW, (NF < 0 || SAMPLER == kScipy) ? 3
 #ifndef DCP_STACK_INT_WAVES
 #define DCP_STACK_INT_WAVES 4   // waves per SIMD the integer instantiations are allocated for (128 VGPRs; at 5 = 96 VGPRs the projection loop spills: 575 us against 435 per uint16 shard)
 #endif
-template <int NF, int SAMPLER, typename T = float>
+// KIND: the coordinate map.  Only the prologue (corner hull, row table, column context, the sixteen coordinates) depends on it; kPersp /
+// kFused: whole frames (row_start = 0, nrows = H) under a tame homography (MapArgs::fast_div = 1: launch_stack_wg_frames declines the
+// others), the float32 coordinates those of remap_wg_kernel bit for bit.
+template <int KIND, int NF, int SAMPLER, typename T = float>
 __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES)) stack_wg_kernel(const StackArgs st, const MapArgs map) {
   constexpr bool kIsF32 = std::is_same<T, float>::value;
   constexpr int ES = (int)sizeof(T);
@@ -1592,7 +1621,8 @@ __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES
   constexpr int kAlignEl = ES >= 4 ? 1 : 4 / ES;               // the box's first column: a dword-aligned byte offset
   static_assert(kIsF32 || SAMPLER == kScipy, "integer and float64 element types blend in scipy's exact order");
   __shared__ __attribute__((aligned(16))) unsigned char s_box[NSLAB][kWgSlabRows * PB];
-  __shared__ double s_row[4][kLdsTH][2];
+  constexpr int RW = KIND == kRadial ? 2 : 4;
+  __shared__ double s_row[4][kLdsTH][RW];
   __shared__ double s_coef[NF < 0 ? kMaxFact : 1];
   using FetchT = Fetch<SAMPLER, true, float>;
 
@@ -1636,23 +1666,29 @@ __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES
   const T* const volT = (const T*)st.vol;
   T* const outT = (T*)st.out;
 
-  // ---- the tile's four corner pixels (lanes 0..3, every wave for itself) -> box
+  // ---- the tile's four corner pixels (lanes 0..3, every wave for itself) -> box (a homography / the fused map: remap_wg_kernel's rule)
   int cx0, cx1, cy0, cy1;
   {
     const double X = (double)min(tile_x * kWgTW + (lane & 1) * (kWgTW - 1), st.W - 1);
     const double Y = st.row_start + (double)min(rblk + ((lane >> 1) & 1) * (kWgTH - 1), st.nrows - 1);
-    const double xu = X - map.xc, yu = Y - map.yc;
-    const double r2 = xu * xu + yu * yu;
-    const double ru = sqrt_rn(r2);
-    double f;
-    if constexpr (NF >= 0) {
-      double le, lo;
-      poly_leads<NF>(map.fact, &le, &lo);
-      f = poly_inline<NF>(map.fact, le, lo, r2, ru);
+    int cxi, cyi;
+    if constexpr (KIND == kRadial) {
+      const double xu = X - map.xc, yu = Y - map.yc;
+      const double r2 = xu * xu + yu * yu;
+      const double ru = sqrt_rn(r2);
+      double f;
+      if constexpr (NF >= 0) {
+        double le, lo;
+        poly_leads<NF>(map.fact, &le, &lo);
+        f = poly_inline<NF>(map.fact, le, lo, r2, ru);
+      } else {
+        f = poly_lds(map.fact, map.nfact, r2, ru);
+      }
+      cxi = (int)round_clip_f32(__builtin_fma(f, xu, map.xc), wmaxf);
+      cyi = (int)round_clip_f32(__builtin_fma(f, yu, map.yc), hmaxf);
     } else {
-      f = poly_lds(map.fact, map.nfact, r2, ru);
+      tile_corner_tap<KIND, NF>(map, wmaxf, hmaxf, X, Y, lane, &cxi, &cyi);
     }
-    const int cxi = (int)round_clip_f32(__builtin_fma(f, xu, map.xc), wmaxf), cyi = (int)round_clip_f32(__builtin_fma(f, yu, map.yc), hmaxf);
     const int xa = __builtin_amdgcn_readlane(cxi, 0), xb = __builtin_amdgcn_readlane(cxi, 1);
     const int xc_ = __builtin_amdgcn_readlane(cxi, 2), xd_ = __builtin_amdgcn_readlane(cxi, 3);
     const int ya = __builtin_amdgcn_readlane(cyi, 0), yb = __builtin_amdgcn_readlane(cyi, 1);
@@ -1675,13 +1711,13 @@ __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES
 
   // ---- coordinates of this wave's 16 rows, once for all projections: slab address (or byte offset inside a projection
   // when the box does not fit) and fractions
-  if (lane < kLdsTH) fill_row<kRadial, 2>(map, s_row[wave], lane, st.row_start + (double)min(r0 + lane, st.nrows - 1));
-  if constexpr (NF < 0) {
+  if (lane < kLdsTH) fill_row<KIND, RW>(map, s_row[wave], lane, st.row_start + (double)min(r0 + lane, st.nrows - 1));
+  if constexpr (NF < 0 && KIND != kPersp) {
     if ((int)threadIdx.x < map.nfact) s_coef[threadIdx.x] = map.fact[threadIdx.x];
     __syncthreads();
   }
   const int rows = __builtin_amdgcn_readfirstlane(max(0, min(kLdsTH, st.nrows - r0)));
-  const ColCtx col = make_col<kRadial, NF>(map, min(x, st.W - 1));
+  const ColCtx col = make_col<KIND, NF>(map, min(x, st.W - 1));
   uint32_t addr[kLdsTH];
   // the two float32 fractions per pixel stay in registers for all projections.  (Integer element types: round 2 kept scipy's four
   // float64 weights instead -- 128 of 168 VGPRs, three waves per SIMD and spills; the conversions back to float64 cost two
@@ -1691,7 +1727,9 @@ __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES
 #pragma unroll
   for (int k = 0; k < kLdsTH; ++k) {
     double xd, yd;
-    map_coord<kRadial, NF, 2>(map, s_row[wave], s_coef, col, k, wmaxf, hmaxf, &xd, &yd);
+    // (a homography: the launcher takes tame ones only, MapArgs::fast_div = 1 -- the division remap_wg_kernel then uses, fixed here at
+    // compile time; an untame one goes frame by frame)
+    map_coord<KIND, NF, RW, (KIND == kRadial ? -1 : 1)>(map, s_row[wave], s_coef, col, k, wmaxf, hmaxf, &xd, &yd);
     const float xc = round_clip_f32(xd, wmaxf), yc = round_clip_f32(yd, hmaxf);
     int xi, yi;
     if constexpr (SAMPLER == kNearest) {
@@ -2459,32 +2497,72 @@ bool stack_wg_would_take(const StackArgs& st, const MapArgs& map, const LaunchOp
   return wg_stack_chunk(st, (dc + 1) / 2, opts.stack_wg >= 2) > 0;
 }
 
-template <int NF, typename T>
+template <int KIND, int NF, typename T>
 static hipError_t launch_stack_wg_t(const StackArgs& st, const MapArgs& map, int sampler, hipStream_t stream) {
   dim3 grid((unsigned)((st.W + kWgTW - 1) / kWgTW), (unsigned)((st.nrows + kWgTH - 1) / kWgTH), (unsigned)((st.D + st.d_chunk - 1) / st.d_chunk));
   if (st.xcd_order == 2) grid.y = 8 * ((grid.y + 7) / 8);            // see the kernel's tile order
   // (A/B) workgroups per CU capped through unused dynamic LDS
   unsigned pad = 0;
   if (st.wg_per_cu >= 1 && st.wg_per_cu <= 3) pad = (unsigned)(160 * 1024 / st.wg_per_cu - 56 * 1024) & ~255u;
+  constexpr int kNoted = KIND == kRadial ? -1 : KIND;                // (the radial kernels keep the name they have always reported)
   if constexpr (std::is_same<T, float>::value) {
-    note_kernel("stack_wg_kernel", -1, NF, sampler);
+    note_kernel("stack_wg_kernel", kNoted, NF, sampler);
     switch (sampler) {
-      case kScipy: hipLaunchKernelGGL((stack_wg_kernel<NF, kScipy, float>), grid, dim3(256), pad, stream, st, map); break;
-      case kF64Lerp: hipLaunchKernelGGL((stack_wg_kernel<NF, kF64Lerp, float>), grid, dim3(256), pad, stream, st, map); break;
-      default: hipLaunchKernelGGL((stack_wg_kernel<NF, kF32Lerp, float>), grid, dim3(256), pad, stream, st, map); break;
+      case kScipy: hipLaunchKernelGGL((stack_wg_kernel<KIND, NF, kScipy, float>), grid, dim3(256), pad, stream, st, map); break;
+      case kF64Lerp: hipLaunchKernelGGL((stack_wg_kernel<KIND, NF, kF64Lerp, float>), grid, dim3(256), pad, stream, st, map); break;
+      default: hipLaunchKernelGGL((stack_wg_kernel<KIND, NF, kF32Lerp, float>), grid, dim3(256), pad, stream, st, map); break;
     }
   } else {
-    note_kernel("stack_wg_kernel", -1, NF, kScipy, sizeof(T) == 8 ? ",float64" : sizeof(T) == 4 ? ",32-bit" : sizeof(T) == 2 ? ",16-bit" : ",8-bit");
-    hipLaunchKernelGGL((stack_wg_kernel<NF, kScipy, T>), grid, dim3(256), pad, stream, st, map);
+    note_kernel("stack_wg_kernel", kNoted, NF, kScipy, sizeof(T) == 8 ? ",float64" : sizeof(T) == 4 ? ",32-bit" : sizeof(T) == 2 ? ",16-bit" : ",8-bit");
+    hipLaunchKernelGGL((stack_wg_kernel<KIND, NF, kScipy, T>), grid, dim3(256), pad, stream, st, map);
   }
   return hipGetLastError();
 }
 
 template <typename T>
 static hipError_t launch_stack_wg_n(const StackArgs& st, const MapArgs& map, int sampler, hipStream_t stream) {
-  if (map.nfact == 5) return launch_stack_wg_t<5, T>(st, map, sampler, stream);
-  if (map.nfact <= 4) return launch_stack_wg_t<4, T>(st, pad4(map), sampler, stream);
-  return launch_stack_wg_t<-1, T>(st, map, sampler, stream);
+  if (map.nfact == 5) return launch_stack_wg_t<kRadial, 5, T>(st, map, sampler, stream);
+  if (map.nfact <= 4) return launch_stack_wg_t<kRadial, 4, T>(st, pad4(map), sampler, stream);
+  return launch_stack_wg_t<kRadial, -1, T>(st, map, sampler, stream);
+}
+
+// the homography alone (no polynomial), or in front of a radial model: up to five coefficients through the NF = 5 instantiation
+// (shorter vectors padded with zeros, see pad4), longer ones looped with the coefficients in LDS
+template <typename T>
+static hipError_t launch_stack_wg_kind(MapKind kind, const StackArgs& st, const MapArgs& map, int sampler, hipStream_t stream) {
+  if (kind == kPersp) return launch_stack_wg_t<kPersp, 0, T>(st, map, sampler, stream);
+  if (map.nfact > 5) return launch_stack_wg_t<kFused, -1, T>(st, map, sampler, stream);
+  MapArgs p = map;
+  for (int i = p.nfact < 0 ? 0 : p.nfact; i < 5; ++i) p.fact[i] = 0.0;
+  p.nfact = 5;
+  return launch_stack_wg_t<kFused, 5, T>(st, p, sampler, stream);
+}
+
+// `st.D` whole frames of one calibration under a homography (kPersp) or the fused perspective o radial map (kFused): float32 (blend
+// `sampler`), uint8 and uint16 (scipy's blend), order 1, map certified at level 2 for its kind with a tame homography; st.row_start = 0,
+// st.nrows = st.H, st.vol / out reinterpreted, strides in elements, proj_bytes the extent of a frame in bytes.
+// *taken = false (and nothing launched): launch the frames one by one.
+hipError_t launch_stack_wg_frames(MapKind kind, const StackArgs& st_in, const MapArgs& map, int dtype, int sampler, const LaunchOpts& opts,
+                                  hipStream_t stream, bool* taken) {
+  *taken = false;
+  if ((kind != kPersp && kind != kFused) || (dtype != kF32 && dtype != kU8 && dtype != kU16) || sampler == kNearest) return hipSuccess;
+  const int es = elem_size(dtype);
+  if (st_in.D == 0 || st_in.nrows != st_in.H || st_in.row_start != 0.0 || !opts.stack_wg || !map.fast_div || !wg_stack_eligible(st_in, map, opts, es))
+    return hipSuccess;
+  StackArgs st = st_in;
+  st.rb0 = st.rbh = 0;
+  st.d_chunk = wg_stack_chunk(st, es >= 4 ? (opts.d_chunk + 1) / 2 : opts.d_chunk, opts.stack_wg >= 2);
+  if (st.d_chunk == 0) return hipSuccess;
+  st.int_exact = opts.int_exact;
+  st.xcd_order = wg_stack_xcd_order(st, opts, es);
+  st.store_wait = opts.store_wait;
+  st.wg_per_cu = opts.wg_per_cu;
+  *taken = true;
+  switch (dtype) {
+    case kU8: return launch_stack_wg_kind<uint8_t>(kind, st, map, kScipy, stream);
+    case kU16: return launch_stack_wg_kind<uint16_t>(kind, st, map, kScipy, stream);
+    default: return launch_stack_wg_kind<float>(kind, st, map, sampler, stream);
+  }
 }
 
 // 8- / 16- / 32-bit integer stacks, float32 coordinates, result of the input's type (unwarp_chunk_slices_backward): st.vol / out

@@ -63,7 +63,8 @@ from .. import _pool
 __all__ = ["unwarp_line_forward", "unwarp_line_backward", "unwarp_image_forward", "calc_residual_hor", "calc_residual_ver",
            "check_distortion", "correct_perspective_line", "unwarp_image_backward", "unwarp_images_backward", "unwarp_slice_backward", "unwarp_chunk_slices_backward",
            "unwarp_slice_backward_centres", "unwarp_chunk_slices_backward_centres",
-           "correct_perspective_image", "unwarp_perspective_fused", "remap_coordinates",
+           "correct_perspective_image", "unwarp_perspective_fused", "correct_perspective_images", "unwarp_perspective_fused_images",
+           "remap_coordinates",
            "generate_radial_map", "generate_fused_map"]
 
 _MODES = ("reflect", "grid-mirror", "constant", "grid-constant", "nearest", "mirror", "grid-wrap", "wrap")
@@ -1162,6 +1163,90 @@ def unwarp_perspective_fused(mat, xcenter, ycenter, list_fact, list_coef, order=
                                          float(xcenter), float(ycenter), fa, nf, ca, order, bcode,
                                          img.mem, img.device, img.stream))
     return out
+
+
+def _frames_under_map(kind, single, mats, xcenter, ycenter, list_fact, list_coef, order, mode, blend, out):
+    """The frames `mats` (a sequence of 2-D arrays or one 3-D array) of one calibration under the homography (kind =
+    F.MAP_PERSPECTIVE) or the fused map (F.MAP_FUSED): a 3-D device array the C ABI can address in place goes to
+    ``dcp_remap_frames_typed``, anything else frame by frame through ``single(frame, out)``."""
+    if len(list_coef) != 8:
+        raise ValueError("!!! Eight coefficients are required !!!")
+    stacked = hasattr(mats, "shape") and len(mats.shape) == 3
+    if hasattr(mats, "shape") and len(mats.shape) != 3:
+        raise ValueError("expected a sequence of 2-D images or one 3-D array (n, height, width)")
+    frames = [mats[i] for i in range(mats.shape[0])] if stacked else list(mats)
+    n = len(frames)
+    order = _check_order_mode(order, mode)
+    out3 = out is not None and hasattr(out, "shape") and len(out.shape) == 3
+    outs = None
+    if out is not None:
+        outs = [out[i] for i in range(n)] if out3 else list(out)
+        if len(outs) != n:
+            raise ValueError("out must hold one array per image")
+    if n == 0:
+        return mats if stacked else []
+    # one call: a 3-D DEVICE array of a real element type, orders 0 / 1, unit column stride, frames that do not overlap (the library
+    # itself falls back to the single-frame kernels where its one-launch kernel does not apply: the same bits either way)
+    if (stacked and order <= 1 and (out is None or out3) and (_is_torch(mats) and mats.is_cuda or _is_cai(mats))
+            and str(_cai_dtype(mats) if _is_cai(mats) else mats.dtype).replace("torch.", "") in F.DTYPE_BY_NAME):
+        img = _Image(mats, 3)
+        (height, width) = img.shape[1:]
+        ps, rs, cs = img.strides
+        if height >= 1 and width >= 1 and cs == 1 and rs >= width and (n == 1 or ps >= (height - 1) * rs + width):
+            fa, nf = F.fact_array(_coefs(list_fact, "list_fact"))
+            ca, _ = F.fact_array(_coefs(list_coef, "list_coef"))
+            whole, optr = img.empty((n, height, width), out=out)
+            F.require_device()
+            F.check(F.lib().dcp_remap_frames_typed(img.ptr, optr, img.code, kind, n, height, width, ps, rs, float(xcenter), float(ycenter),
+                                                   fa, nf, ca, order, _blend_code(blend), img.mem, img.device, img.stream))
+            return whole
+    res = [single(frames[i], None if outs is None else outs[i]) for i in range(n)]
+    if not stacked:
+        return res
+    if out3:
+        return out
+    if _is_torch(res[0]):
+        import torch
+        return torch.stack(res)
+    if isinstance(res[0], F.DeviceArray):
+        return res
+    return np.stack(res)
+
+
+def correct_perspective_images(mats, list_coef, order=1, mode="reflect", *, blend=None, out=None):
+    """
+    :func:`correct_perspective_image` (reference ``postprocessing.py:444-459, 462-492``) over the frames of one homography
+    in ONE call -- a detector stack or a video whose every frame gets the same perspective correction.
+
+    Parameters
+    ----------
+    mats : sequence of 2D arrays, or one 3D array (n, height, width)
+        The frames (NumPy arrays or device arrays), under one calibration.
+    list_coef, order, mode : as :func:`correct_perspective_image`.
+
+    Returns
+    -------
+    list of 2D arrays (a sequence was given) or one 3D array of the same kind (a 3D array was given); every frame is
+    bit-identical to what :func:`correct_perspective_image` returns for it under the same ``blend``.  A 3D device array
+    with unit column stride and non-overlapping frames goes to ``dcp_remap_frames_typed``: float32, uint8 and uint16 at
+    order 1 under a certified homography run in one kernel launch (the coordinates of a tile are evaluated once for all
+    frames); anything else is processed frame by frame.
+    """
+    return _frames_under_map(F.MAP_PERSPECTIVE, lambda f, o: correct_perspective_image(f, list_coef, order, mode, blend=blend, out=o),
+                             mats, 0.0, 0.0, [], list_coef, order, mode, blend, out)
+
+
+def unwarp_perspective_fused_images(mats, xcenter, ycenter, list_fact, list_coef, order=1, mode="reflect", *, blend=None,
+                                    out=None):
+    """
+    :func:`unwarp_perspective_fused` (BASELINE config 3: perspective and radial correction in one resampling, in place of
+    the reference's two passes ``examples/readthedocs_demo/demo_05.py:127,147``) over the frames of one calibration in ONE
+    call.  ``mats``, the return conventions, ``out=`` and the routing are those of :func:`correct_perspective_images`;
+    every frame is bit-identical to what :func:`unwarp_perspective_fused` returns for it under the same ``blend``.
+    """
+    return _frames_under_map(F.MAP_FUSED,
+                             lambda f, o: unwarp_perspective_fused(f, xcenter, ycenter, list_fact, list_coef, order, mode, blend=blend, out=o),
+                             mats, xcenter, ycenter, list_fact, list_coef, order, mode, blend, out)
 
 
 def remap_coordinates(mat, ycoords, xcoords, order=1, mode="reflect", *, blend=None):

@@ -394,6 +394,23 @@ int dcp_coordinate_map_f32(float* ymap, float* xmap, int64_t height, int64_t wid
                            double ycenter, const double* list_fact, int nfact, const double* list_coef, int mem_kind,
                            int device, void* stream);
 
+/* `nframes` frames of ONE calibration under the homography (map_kind DCP_MAP_PERSPECTIVE: the coordinates of
+ * discorpy/post/postprocessing.py:444-459 and the map_coordinates call of :486-492; xcenter, ycenter and list_fact ignored) or under the
+ * one-pass perspective -> radial map of dcp_unwarp_fused_f32 (DCP_MAP_FUSED: both) -- the loop a caller writes around
+ * examples/readthedocs_demo/demo_05.py:127,147 for every frame of a run, a detector stack or a video.  DCP_MAP_RADIAL is refused: frames
+ * under the radial map alone are the projections of a stack (dcp_unwarp_stack_rows_f32 / _typed).
+ *   src   frames `frame_stride` elements apart (not overlapping), rows `row_stride` elements apart, unit column stride
+ *   dst   dense (nframes, height, width), elements of `dtype` (any DCP_DTYPE_*) like the source
+ *   order 0 or 1; blend_mode applies to DCP_DTYPE_F32 only (every other type blends in scipy's order)
+ * Device frames of float32, uint8 or uint16 at order 1 whose map holds the level-2 tile certificate of its kind run in ONE launch
+ * (stack_wg_kernel: the coordinates of a 128 x 32 tile evaluated once for all frames of a depth chunk) when the launch is large enough;
+ * everything else -- order 0, other element types, an uncertified or untame homography, few small frames, host memory -- goes through
+ * the single-frame entry point frame by frame on the same stream.  Every frame equals what dcp_perspective_image_f32 / _typed or
+ * dcp_unwarp_fused_f32 / _typed give for it bit for bit either way; dcp_debug_last_kernel() names the path taken.  nframes = 0 is DCP_OK. */
+int dcp_remap_frames_typed(const void* src, void* dst, int dtype, int map_kind, int64_t nframes, int64_t height, int64_t width,
+                           int64_t frame_stride, int64_t row_stride, double xcenter, double ycenter, const double* list_fact,
+                           int nfact, const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the
