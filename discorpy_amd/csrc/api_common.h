@@ -152,8 +152,9 @@ static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPer
 // is of every stack call.  Executors: the tuned float32 kernels within 32-bit offsets (unwarp_kernels.hip), the generic ones for
 // orders 0 / 1 on any element type (typed_kernels.hip, or remap_wg_kernel / the one-channel colour kernel where they qualify),
 // interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip), the forward scatter of any element
-// type (api_spline.cpp for its winner plane, forward_kernels.hip).
-enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline, kExecForward };
+// type (api_spline.cpp for its winner plane, forward_kernels.hip), interleaved channels at spline orders 2..5 (api_spline.cpp,
+// spline_color_kernels.hip).
+enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline, kExecForward, kExecColourSpline };
 struct FrameCall {
   FrameExec exec;
   dcp::MapKind kind;
@@ -217,6 +218,9 @@ int host_round_trip(const HostTrip& t, hipStream_t st, Launch&& launch) {
 
 // api_spline.cpp: the spline executor (c.exec == kExecSpline; the device is selected)
 int run_spline(const FrameCall& c);
+// api_spline.cpp: interleaved channels at orders 2..5 (c.exec == kExecColourSpline; the device is selected): the single-plane prefilter
+// once per channel into a workspace slot of c.channels + 1 planes, then one gather launch
+int run_spline_color(const FrameCall& c);
 // api_spline.cpp: the forward-scatter executor (c.exec == kExecForward; the device is selected); its winner plane is leased from the
 // spline workspace
 int run_forward(const FrameCall& c);

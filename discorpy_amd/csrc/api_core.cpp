@@ -736,7 +736,7 @@ int dcp_debug_bounds(uint64_t* out, int n, int reset) {
 #endif
   out[0] = out[1] = out[2] = out[3] = 0;
   DCP_HIP(hipDeviceSynchronize());
-  hipError_t (*readers[3])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_color, dcp::read_bounds_spline};
+  hipError_t (*readers[4])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_color, dcp::read_bounds_spline, dcp::read_bounds_spline_color};
   for (auto rd : readers) {
     unsigned long long v[4];
     DCP_HIP(rd(v, reset != 0));

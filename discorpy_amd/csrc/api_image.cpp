@@ -428,6 +428,15 @@ int make_frame_call(FrameCall* c, FrameExec exec, dcp::MapKind kind, const void*
     else c->map.tile_dev_ok = cert && (kind != dcp::kFused || g_fused_wg.load()) && colour_boxes_fit(kind, c->map, H, W) ? 2 : 0;
     return DCP_OK;
   }
+  if (exec == kExecColourSpline) {
+    // interleaved channels at orders 2..5: the ranges of the colour entry points and of the typed spline entry points together; the
+    // element type, order, boundary mode and size checks of the single-plane spline call follow below
+    if (channels < 1 || channels > 4) return fail(DCP_ERR_INVALID_ARG, "channels = %d outside [1, 4] (the spline orders on interleaved channels)", channels);
+    if (cs < channels) return fail(DCP_ERR_INVALID_ARG, "pixel stride %lld smaller than %d channels", (long long)cs, channels);
+    if ((rc = check_image_typed(src, dst, dtype, H, W, rs, cs)) != DCP_OK) return rc;
+    if (rs < (W - 1) * cs + channels && H > 1)
+      return fail(DCP_ERR_INVALID_ARG, "row stride %lld overlaps rows of %lld pixels", (long long)rs, (long long)W);
+  }
   if (exec == kExecTuned) {
     if (kind == dcp::kCoords && (mode < 0 || mode > 7)) return fail(DCP_ERR_INVALID_ARG, "unknown boundary mode %d", mode);
     if ((rc = sampler_of(order, blend_mode, &c->sampler)) != DCP_OK) return rc;
@@ -541,6 +550,7 @@ int run_frame(const FrameCall& c) {
   DeviceScope scope(c.device);
   if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", c.device, hipGetErrorString(scope.status));
   if (c.exec == kExecSpline) return run_spline(c);
+  if (c.exec == kExecColourSpline) return run_spline_color(c);
   if (c.exec == kExecForward) return run_forward(c);
   if (!c.host) {
     DCP_HIP(launch_frame(c, c.src, c.dst, c.ycoord, c.xcoord, c.rs, c.cs, 0, 0, c.stream));
@@ -874,6 +884,40 @@ int dcp_unwarp_fused_color_image(const void* src, void* dst, int dtype, int64_t 
   FrameCall c;
   const int rc = make_frame_call(&c, kExecColour, dcp::kFused, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
                                  xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, blend_mode, 0, 1, mem_kind, device, stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+// The three colour entry points at spline orders 2..5.  Each channel's result is that of the single-plane call on its view, down to the
+// homography's division: the float32 single-plane spline entry point divides plainly, the typed one with the refined reciprocal where
+// the homography is tame (dcp_perspective_image_spline_f32 above) -- the same choice is made here from the element type.
+int dcp_unwarp_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                  int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact, int order,
+                                  int boundary_mode, int mem_kind, int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColourSpline, dcp::kRadial, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
+                                 xcenter, ycenter, list_fact, nfact, nullptr, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device,
+                                 stream);
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_perspective_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels,
+                                       int64_t src_row_stride, int64_t src_pixel_stride, const double* list_coef, int order, int boundary_mode,
+                                       int mem_kind, int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColourSpline, dcp::kPersp, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
+                                 0.0, 0.0, nullptr, 0, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind, device, stream);
+  if (dtype == dcp::kF32) c.map.fast_div = 0;
+  return rc != DCP_OK ? rc : run_frame(c);
+}
+
+int dcp_unwarp_fused_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels,
+                                        int64_t src_row_stride, int64_t src_pixel_stride, double xcenter, double ycenter,
+                                        const double* list_fact, int nfact, const double* list_coef, int order, int boundary_mode, int mem_kind,
+                                        int device, void* stream) {
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecColourSpline, dcp::kFused, src, dst, dtype, height, width, src_row_stride, src_pixel_stride, channels,
+                                 xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind,
+                                 device, stream);
   return rc != DCP_OK ? rc : run_frame(c);
 }
 

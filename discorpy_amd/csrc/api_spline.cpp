@@ -155,8 +155,8 @@ int release_spline_workspace() {
   return DCP_OK;
 }
 
-int run_spline(const FrameCall& c) {
-  hipStream_t st = c.stream;
+// The SplineArgs of a validated spline call, all but the workspace planes and the source pointer.
+static dcp::SplineArgs spline_args_of(const FrameCall& c) {
   dcp::SplineArgs a;
   memset(&a, 0, sizeof(a));
   a.H = (int32_t)c.H;
@@ -178,6 +178,14 @@ int run_spline(const FrameCall& c) {
     for (int p = 0; p < a.npoles; ++p)
       a.zpow[axis][p] = std::pow(a.poles[p], a.filter_kind == dcp::kSplMirror ? n - 1.0 : n);
   }
+  a.src_stride = (int32_t)c.rs;
+  a.src_cstride = (int32_t)c.cs;
+  return a;
+}
+
+int run_spline(const FrameCall& c) {
+  hipStream_t st = c.stream;
+  dcp::SplineArgs a = spline_args_of(c);
   const size_t plane = (size_t)a.Hp * (size_t)a.Wp * sizeof(double);
   int cur_dev = 0;
   DCP_HIP(hipGetDevice(&cur_dev));                           // (run_frame has selected it)
@@ -187,8 +195,6 @@ int run_spline(const FrameCall& c) {
   SlotGuard guard{slot, st};
   a.coef = (double*)slot->buf;
   a.scratch = a.coef + (size_t)a.Hp * (size_t)a.Wp;
-  a.src_stride = (int32_t)c.rs;
-  a.src_cstride = (int32_t)c.cs;
   dcp::CoordArgs ca;
   memset(&ca, 0, sizeof(ca));
   ca.npts = c.npts;
@@ -215,6 +221,38 @@ int run_spline(const FrameCall& c) {
     ca.ycoord = dy;
     ca.xcoord = dx;
     return dcp::launch_spline(a, c.kind, c.map, ca, ddst, st);
+  });
+}
+
+// Interleaved (H, W, channels) image at orders 2..5: the workspace slot holds channels + 1 planes -- the coefficients of every channel
+// and the prefilter's second plane --, the single-plane prefilter runs once per channel on that channel's column-strided view, one
+// gather launch follows.  Host memory: the interleaved extent goes up once, the dense result comes back once.
+int run_spline_color(const FrameCall& c) {
+  hipStream_t st = c.stream;
+  dcp::SplineArgs a = spline_args_of(c);
+  const size_t plane = (size_t)a.Hp * (size_t)a.Wp * sizeof(double);
+  int cur_dev = 0;
+  DCP_HIP(hipGetDevice(&cur_dev));                           // (run_frame has selected it)
+  if (cur_dev < 0 || cur_dev >= 64) return fail(DCP_ERR_UNSUPPORTED, "device index %d", cur_dev);
+  SplineWorkspace::Slot* slot = nullptr;
+  DCP_HIP(g_spline_ws.acquire((size_t)(c.channels + 1) * plane, st, cur_dev, &slot));
+  SlotGuard guard{slot, st};
+  a.coef = (double*)slot->buf;
+  a.scratch = a.coef + (size_t)c.channels * (size_t)a.Hp * (size_t)a.Wp;
+  if (!c.host) {
+    a.src = c.src;
+    DCP_HIP(dcp::launch_spline_color(a, c.kind, c.map, c.channels, c.dst, st));
+    return DCP_OK;
+  }
+  const size_t esz = (size_t)dcp::elem_size(c.dtype);
+  HostTrip t;
+  t.src = c.src;
+  t.row_bytes = t.pitch = (size_t)((c.H - 1) * c.rs + (c.W - 1) * c.cs + c.channels) * esz;
+  t.dst = c.dst;
+  t.out_bytes = (size_t)c.H * (size_t)c.W * (size_t)c.channels * esz;
+  return host_round_trip(t, st, [&](const void* dsrc, void* ddst, void*, void*) {
+    a.src = dsrc;
+    return dcp::launch_spline_color(a, c.kind, c.map, c.channels, ddst, st);
   });
 }
 

@@ -18,6 +18,7 @@
 #include "dcp_internal.h"
 #include "dcp_device.h"
 #include "dcp_lab.h"
+#include "spline_device.h"
 #include <cstdio>
 #include <type_traits>
 
@@ -27,7 +28,6 @@
 
 namespace dcp {
 
-constexpr int kSplBlock = 256;
 int g_spline_wg = 1;             // 0: the (order + 1)^2 taps always gathered from global memory (option spline_wg)
 void set_spline_wg(int v) { g_spline_wg = v; }
 int get_spline_wg() { return g_spline_wg; }
@@ -1305,114 +1305,6 @@ __global__ void __launch_bounds__(kSplBlock) spline_transpose_kernel(const doubl
     if (bx + j < cols && by + tx < rows) out[(size_t)(bx + j) * rows + (by + tx)] = tile[tx][j];
 }
 
-// x / D, correctly rounded, for the constants of the weight polynomials: q = x * RN(1/D), one exact residual, one
-// correction (Markstein) -- three instructions where the compiler's IEEE division takes about twenty, and the weights
-// need up to eight divisions per pixel.  |x| is O(1) here: nothing leaves the normal range.
-template <int D>
-__device__ __forceinline__ double div_c(double x) {
-  constexpr double r = 1.0 / (double)D;
-  const double q = x * r;
-  const double e = __builtin_fma(-(double)D, q, x);
-  return __builtin_fma(e, r, q);
-}
-
-// centred B-spline weights (the expressions of spline_weights() in the oracle); returns the first tap
-// FAST (the factorised gather only, where the sum is not scipy's to the last bit anyway): the cubic weights as fused polynomials,
-// y^2 (y / 2 - 1) + 2 / 3 and z^3 / 6 -- 15 operations per axis instead of 27; each weight within one float64 ulp of scipy's form.
-template <int ORDER, bool FAST = false>
-__device__ __forceinline__ int spline_weights(double x, double* w) {
-  double s;
-  if constexpr (ORDER & 1) s = __builtin_floor(x);
-  else s = __builtin_floor(x + 0.5);
-  const double t = x - s;
-  const int start = (int)s - ORDER / 2;
-  double y = t, z = 1.0 - t, t2;
-  if constexpr (ORDER == 3 && FAST) {
-    w[1] = __builtin_fma(y * y, __builtin_fma(y, 0.5, -1.0), 2.0 / 3.0);
-    w[2] = __builtin_fma(z * z, __builtin_fma(z, 0.5, -1.0), 2.0 / 3.0);
-    w[0] = (z * z) * (z * (1.0 / 6.0));
-    w[3] = 1.0 - w[0] - w[1] - w[2];
-  } else if constexpr (ORDER == 4 && FAST) {
-    // (round 6) the quartic and quintic weights as fused Horner chains in the same variables as scipy's expressions: 21 / 29 operations
-    // per axis instead of 37 / 53, every weight within a few float64 ulps of scipy's form (the constants 1/6, 1/24, 1/120 rounded once)
-    t2 = t * t;
-    w[2] = __builtin_fma(t2, __builtin_fma(t2, 0.25, -0.625), 115.0 / 192.0);
-    y = 1.0 + t;
-    z = 1.0 - t;
-    w[1] = __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, -1.0 / 6.0, 5.0 / 6.0), -1.25), 5.0 / 24.0), 55.0 / 96.0);
-    w[3] = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, -1.0 / 6.0, 5.0 / 6.0), -1.25), 5.0 / 24.0), 55.0 / 96.0);
-    y = 0.5 - t;
-    y *= y;
-    w[0] = (y * y) * (1.0 / 24.0);
-    w[4] = 1.0 - w[0] - w[1] - w[2] - w[3];
-  } else if constexpr (ORDER == 5 && FAST) {
-    t2 = y * y;
-    w[2] = __builtin_fma(t2, __builtin_fma(t2, __builtin_fma(y, -1.0 / 12.0, 0.25), -0.5), 0.55);
-    t2 = z * z;
-    w[3] = __builtin_fma(t2, __builtin_fma(t2, __builtin_fma(z, -1.0 / 12.0, 0.25), -0.5), 0.55);
-    w[0] = (t2 * t2) * (z * (1.0 / 120.0));
-    y += 1.0;
-    w[1] = __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, 1.0 / 24.0, -0.375), 1.25), -1.75), 0.625), 0.425);
-    y = z + 1.0;
-    w[4] = __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, __builtin_fma(y, 1.0 / 24.0, -0.375), 1.25), -1.75), 0.625), 0.425);
-    w[5] = 1.0 - w[0] - w[1] - w[2] - w[3] - w[4];
-  } else if constexpr (ORDER == 2) {
-    w[1] = 0.75 - t * t;
-    y = 0.5 + t;
-    w[2] = 0.5 * y * y;
-    w[0] = 1.0 - w[1] - w[2];
-  } else if constexpr (ORDER == 3) {
-    w[1] = div_c<6>(y * y * (y - 2.0) * 3.0 + 4.0);
-    w[2] = div_c<6>(z * z * (z - 2.0) * 3.0 + 4.0);
-    w[0] = div_c<6>(z * z * z);
-    w[3] = 1.0 - w[0] - w[1] - w[2];
-  } else if constexpr (ORDER == 4) {
-    t2 = t * t;
-    w[2] = t2 * (t2 * 0.25 - 0.625) + 115.0 / 192.0;
-    y = 1.0 + t;
-    z = 1.0 - t;
-    w[1] = y * (y * (div_c<6>(y * (5.0 - y)) - 1.25) + 5.0 / 24.0) + 55.0 / 96.0;
-    w[3] = z * (z * (div_c<6>(z * (5.0 - z)) - 1.25) + 5.0 / 24.0) + 55.0 / 96.0;
-    y = 0.5 - t;
-    y *= y;
-    w[0] = div_c<24>(y * y);
-    w[4] = 1.0 - w[0] - w[1] - w[2] - w[3];
-  } else {
-    t2 = y * y;
-    w[2] = t2 * (t2 * (0.25 - div_c<12>(y)) - 0.5) + 0.55;
-    t2 = z * z;
-    w[3] = t2 * (t2 * (0.25 - div_c<12>(z)) - 0.5) + 0.55;
-    y += 1.0;
-    w[1] = y * (y * (y * (y * (div_c<24>(y) - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
-    y = z + 1.0;
-    w[4] = y * (y * (y * (y * (div_c<24>(y) - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
-    t2 = z * z;
-    w[0] = div_c<120>(t2 * t2 * z);
-    w[5] = 1.0 - w[0] - w[1] - w[2] - w[3] - w[4];
-  }
-  return start;
-}
-
-__device__ __forceinline__ int spline_fold(int i, int n, int mode) {
-  if (i >= 0 && i < n) return i;
-  if (mode == kModeReflect || mode == kModeGridMirror) {
-    const int s2 = 2 * n;
-    i %= s2;
-    if (i < 0) i += s2;
-    return i < n ? i : s2 - 1 - i;
-  }
-  if (mode == kModeGridWrap) {
-    i %= n;
-    return i < 0 ? i + n : i;
-  }
-  if (mode == kModeNearest || mode == kModeGridConstant) return i < 0 ? 0 : n - 1;
-  if (n == 1) return 0;
-  const int s2 = 2 * n - 2;
-  i %= s2;
-  if (i < 0) i += s2;
-  return i < n ? i : s2 - i;
-}
-
 // MAPKIND 0 radial, 1 perspective, 2 explicit coordinates (dst[i] for point i), 3 fused perspective -> radial
 template <int MAPKIND, int ORDER>
 __global__ void __launch_bounds__(kSplBlock) spline_remap_kernel(const SplineArgs a, const MapArgs map, const CoordArgs ca,
@@ -1495,10 +1387,6 @@ __global__ void __launch_bounds__(kSplBlock) spline_remap_kernel(const SplineArg
 // taps of a pixel are then LDS reads instead of global gathers.  A tile whose box does not fit the slab or reaches
 // over the edge of the coefficient plane (there the taps fold according to the boundary mode) takes the global
 // gather of spline_remap_kernel for all its pixels.  Radial and perspective maps.
-constexpr int kSwTW = 128, kSwTH = 32;             // workgroup tile
-constexpr int kSwBoxW = 144, kSwBoxH = 45;         // slab: 144 x 45 float64 = 51 840 B; with the row tables three workgroups per CU
-constexpr int kSwCH = kSwBoxW * 8 / 16;            // 16-byte chunks per slab row
-constexpr int kSwNJ = (kSwBoxH * kSwCH + 255) / 256;   // loads per wave that cover the slab: 13
 
 // NF: length of the radial polynomial (5: coefficients from the kernel arguments, shorter vectors padded with zeros by the
 // launcher -- fma(r2, 0, a) = a exactly; -1: any length, coefficients staged in LDS).  Phase 1 is remap_wg_kernel's: a row table
@@ -1746,8 +1634,9 @@ static hipError_t launch_remap_order(const SplineArgs& a, const MapArgs& map, co
 
 DCP_DEFINE_BOUNDS_READER(read_bounds_spline)
 
-hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, const CoordArgs& ca, void* dst,
-                         hipStream_t stream) {
+// The prefilter of one plane: a.src (a.src_stride / a.src_cstride: a channel of an interleaved image is a column-strided view) ->
+// B-spline coefficients in a.coef, a.scratch the second plane.  `desc` receives the kernels' names as dcp_last_kernel reports them.
+hipError_t launch_spline_prefilter(const SplineArgs& a, hipStream_t stream, char* desc, size_t desc_len) {
   // prefilter: axis 0 on the (Hp x Wp) plane, transpose, axis 1 as axis 0 of the (Wp x Hp) plane,
   // transpose back.  Two planes ping-pong: a.coef (A) and a.scratch (B); the result ends in A.
   double lam = 1.0;
@@ -1997,21 +1886,34 @@ hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, 
     hipLaunchKernelGGL(spline_transpose_kernel, dim3((unsigned)((a.Hp + 31) / 32), (unsigned)((a.Wp + 31) / 32)),
                        dim3(kSplBlock), 0, stream, (const double*)a.scratch, a.coef, a.Wp, a.Hp);
   }
-  hipError_t e = hipGetLastError();
+  {
+    const char* colk = col_lds ? "spline_col_lds_kernel" : col_stream ? "spline_col_stream_kernel" : "spline_tile_filter_kernel";
+    const char* rowk = row_scan ? "spline_row_scan_kernel" : row_lds ? "spline_row_lds_kernel" : "spline_tile_filter_kernel";
+    if (fused2d) snprintf(desc, desc_len, "spline_prefilter2d_kernel%s", two_pass ? " x 2" : "");
+    else if (!tiled) snprintf(desc, desc_len, "spline_causal / anticausal / transpose kernels");
+    else if (!col_stream && !row_scan && !row_lds) snprintf(desc, desc_len, "spline_tile_filter_kernel x 2");
+    else snprintf(desc, desc_len, "%s + %s", colk, rowk);
+  }
+  return hipGetLastError();
+}
+
+// certified radial / perspective maps on frames of at least one workgroup tile: the taps out of LDS (spline_wg_kernel, spline_wg_color_kernel)
+bool spline_wg_takes(const SplineArgs& a, MapKind kind, const MapArgs& map) {
+  return (kind == kRadial || kind == kPersp) && map.tile_dev_ok >= 2 && g_spline_wg && a.H >= kSwTH && a.W >= kSwTW &&
+         (int64_t)a.Hp * a.Wp * 8 < ((int64_t)1 << 32) && a.Hp < 65535 * kSwTH;
+}
+
+hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, const CoordArgs& ca, void* dst,
+                         hipStream_t stream) {
+  char desc[128];
+  hipError_t e = launch_spline_prefilter(a, stream, desc, sizeof(desc));
   if (e != hipSuccess) return e;
   const int64_t total = kind == kCoords ? ca.npts : (int64_t)a.H * a.W;
   if (total == 0) return hipSuccess;
-  // certified radial / perspective maps on frames of at least one workgroup tile: the taps out of LDS
-  const bool wg = (kind == kRadial || kind == kPersp) && map.tile_dev_ok >= 2 && g_spline_wg && a.H >= kSwTH && a.W >= kSwTW &&
-                  (int64_t)a.Hp * a.Wp * 8 < ((int64_t)1 << 32) && a.Hp < 65535 * kSwTH;
+  const bool wg = spline_wg_takes(a, kind, map);
   {
     char name[160];
-    const char* colk = col_lds ? "spline_col_lds_kernel" : col_stream ? "spline_col_stream_kernel" : "spline_tile_filter_kernel";
-    const char* rowk = row_scan ? "spline_row_scan_kernel" : row_lds ? "spline_row_lds_kernel" : "spline_tile_filter_kernel";
-    if (fused2d) snprintf(name, sizeof(name), "spline_prefilter2d_kernel%s + %s<order=%d>", two_pass ? " x 2" : "", wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
-    else if (!tiled) snprintf(name, sizeof(name), "spline_causal / anticausal / transpose kernels + %s<order=%d>", wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
-    else if (!col_stream && !row_scan && !row_lds) snprintf(name, sizeof(name), "spline_tile_filter_kernel x 2 + %s<order=%d>", wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
-    else snprintf(name, sizeof(name), "%s + %s + %s<order=%d>", colk, rowk, wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
+    snprintf(name, sizeof(name), "%s + %s<order=%d>", desc, wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
     set_last_kernel_name(name);
   }
   if (wg) {

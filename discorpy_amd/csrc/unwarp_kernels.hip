@@ -1930,8 +1930,9 @@ __global__ void __launch_bounds__(256, (sizeof(T) >= 4 ? 3 : DCP_STACK_INT_WAVES
 // ------------------------------------------------------------------ launchers
 
 // Name of the kernel the calling thread launched last (dcp_debug_last_kernel): tests and bench.py use it to state --
-// and assert -- which kernel a call really took.
-static thread_local char g_last_kernel[96] = "";
+// and assert -- which kernel a call really took.  (The longest name is a spline colour call's: a two-kernel prefilter description of
+// up to 52 characters, " + " and the gather's 46 -- 101 in all.)
+static thread_local char g_last_kernel[192] = "";
 static const char* kind_name(int k) { return k == kRadial ? "Radial" : k == kPersp ? "Persp" : "Fused"; }
 static const char* sampler_name(int s) { return s == kNearest ? "nearest" : s == kScipy ? "scipy" : s == kF64Lerp ? "f64lerp" : "f32lerp"; }
 static void note_kernel(const char* kernel, int kind, int nf, int sampler, const char* extra = "") {

@@ -3,7 +3,8 @@
 ``unwarp_color_image_backward`` has the signature and semantics of the reference
 (``/root/reference/discorpy/util/utility.py:278-342``): optional padding, then the backward radial
 unwarp of every channel at the SAME float32 coordinates -- one launch on the interleaved image for
-orders 0 / 1, plane by plane through :mod:`discorpy_amd.post.postprocessing` otherwise.
+orders 0 / 1, one gather launch behind a prefilter per channel for orders 2..5 on up to four channels
+(``dcp_unwarp_color_image_spline``), plane by plane through :mod:`discorpy_amd.post.postprocessing` otherwise.
 
 ``correct_perspective_color_image`` and ``unwarp_perspective_fused_color_image`` do the same for the homography and for the
 one-pass perspective -> radial map: what the reference's demos write as a loop of ``post.correct_perspective_image`` over
@@ -168,6 +169,40 @@ def _homography_interleaved(mat, radial, list_coef, order, blend=None):
     return out
 
 
+def _spline_interleaved(mat, radial, list_coef, order, mode, blend):
+    """(H, W, C) interleaved image, C = 1..4, at spline orders 2..5 in one call: the single-plane prefilter once per channel, then
+    one gather that evaluates a pixel's coordinate once for all its channels.  radial = (xcenter, ycenter, list_fact) or None,
+    list_coef the homography or None: the radial map (dcp_unwarp_color_image_spline), the homography
+    (dcp_perspective_color_image_spline) or the one-pass perspective -> radial map (dcp_unwarp_fused_color_image_spline).
+    Every channel equals the single-plane function on ``mat[:, :, c]`` bit for bit."""
+    F = _pp.F
+    img, rs, ps = _interleaved_image(mat)
+    h, w, c = img.shape
+    mcode = _pp._spline_mode(mode, blend)
+    if list_coef is not None:
+        ca, _ = F.fact_array(_pp._coefs(list_coef, "list_coef"))
+    if radial is not None:
+        fa, nf = F.fact_array(_pp._coefs(radial[2], "list_fact"))
+    out, optr = img.empty((h, w, c))
+    F.require_device()
+    if list_coef is None:
+        F.check(F.lib().dcp_unwarp_color_image_spline(img.ptr, optr, img.code, h, w, c, rs, ps, float(radial[0]), float(radial[1]), fa, nf,
+                                                      order, mcode, img.mem, img.device, img.stream))
+    elif radial is None:
+        F.check(F.lib().dcp_perspective_color_image_spline(img.ptr, optr, img.code, h, w, c, rs, ps, ca, order, mcode, img.mem, img.device,
+                                                           img.stream))
+    else:
+        F.check(F.lib().dcp_unwarp_fused_color_image_spline(img.ptr, optr, img.code, h, w, c, rs, ps, float(radial[0]), float(radial[1]),
+                                                            fa, nf, ca, order, mcode, img.mem, img.device, img.stream))
+    return out
+
+
+def _spline_one_call(order, channels):
+    """Do the interleaved-channel spline entry points take this call?  Orders 2..5, 1 to 4 channels (and an image that is not empty:
+    the single-plane functions keep their own answer to that)."""
+    return 2 <= order <= 5 and 1 <= channels <= 4
+
+
 def _one_launch(order, blend, channels):
     """Do the interleaved-channel entry points take this call?  Orders 0 / 1, scipy's blend or its one-ulp factorisation
     (names are case-insensitive), 1 to 64 channels."""
@@ -209,7 +244,8 @@ def correct_perspective_color_image(mat, list_coef, order=1, mode="reflect", map
     list_coef : list of floats
         Coefficients of the backward-mapping matrix (c1..c8, (x, y) convention).
     order : int, optional.
-        The order of the spline interpolation (0..5); orders 2..5 go plane by plane.
+        The order of the spline interpolation (0..5); orders 2..5 take one call for up to four channels (a prefilter per
+        channel, one gather), more channels and ``map_index=`` go plane by plane.
     mode : str, optional
         Boundary mode of scipy's spline interpolation; inert for order <= 1.
     map_index : array_like
@@ -230,6 +266,8 @@ def correct_perspective_color_image(mat, list_coef, order=1, mode="reflect", map
         return res
     if map_index is None and _one_launch(order, blend, mat.shape[2]):
         return _homography_interleaved(mat, None, list_coef, order, blend)
+    if map_index is None and _spline_one_call(order, mat.shape[2]) and mat.shape[0] > 0 and mat.shape[1] > 0:
+        return _spline_interleaved(mat, None, list_coef, order, mode, blend)
     return _plane_by_plane(mat, lambda plane: _pp.correct_perspective_image(plane, list_coef, order=order, mode=mode,
                                                                             map_index=map_index, blend=blend))
 
@@ -252,7 +290,8 @@ def unwarp_perspective_fused_color_image(mat, xcenter, ycenter, list_fact, list_
     list_coef : list of floats
         Coefficients of the backward-mapping matrix (c1..c8, (x, y) convention).
     order : int, optional.
-        The order of the spline interpolation (0..5); orders 2..5 go plane by plane.
+        The order of the spline interpolation (0..5); orders 2..5 take one call for up to four channels (a prefilter per
+        channel, one gather), more channels go plane by plane.
     mode : str, optional
         Boundary mode of scipy's spline interpolation; inert for order <= 1.
 
@@ -272,6 +311,8 @@ def unwarp_perspective_fused_color_image(mat, xcenter, ycenter, list_fact, list_
         return res
     if _one_launch(order, blend, mat.shape[2]):
         return _homography_interleaved(mat, (xcenter, ycenter, list_fact), list_coef, order, blend)
+    if _spline_one_call(order, mat.shape[2]) and mat.shape[0] > 0 and mat.shape[1] > 0:
+        return _spline_interleaved(mat, (xcenter, ycenter, list_fact), list_coef, order, mode, blend)
     return _plane_by_plane(mat, lambda plane: _pp.unwarp_perspective_fused(plane, xcenter, ycenter, list_fact, list_coef, order=order,
                                                                            mode=mode, blend=blend))
 
@@ -284,15 +325,16 @@ def unwarp_color_image_backward(mat, xcenter, ycenter, list_fact, order=1, mode=
     Parameters
     ----------
     mat : array_like
-        2D/3D float32 array (H, W) or (H, W, C); NumPy array or ROCm torch tensor.
+        2D/3D array (H, W) or (H, W, C); NumPy array or ROCm torch tensor.
     xcenter, ycenter : float
         Center of distortion (of the UNPADDED image, as in the reference).
     list_fact : list of float
         Polynomial coefficients of the backward model.
     order : int, optional.
-        The order of the spline interpolation (0 or 1).
+        The order of the spline interpolation (0..5); orders 2..5 take one call for up to four channels (a prefilter per
+        channel, one gather), more channels go plane by plane.
     mode : str, optional
-        Accepted for compatibility; inert for order <= 1.
+        Boundary mode of scipy's spline interpolation; inert for order <= 1.
     pad : bool, int, or tuple of int.
         Use to keep the original view.  ``True``: the width is calculated automatically.
     pad_mode : str
@@ -330,8 +372,11 @@ def unwarp_color_image_backward(mat, xcenter, ycenter, list_fact, order=1, mode=
     # (`blend` names are case-insensitive everywhere, here too: "SciPy" must not fall to the plane-by-plane path -- ADVICE r4)
     if order <= 1 and (blend is None or str(blend).lower() in ("scipy", "exact", "f64lerp", "f64")) and 1 <= mat_pad.shape[2] <= 64:
         return _unwarp_interleaved(mat_pad, xcenter, ycenter, list_fact, order, blend)
-    # channels as dense planes through the batched entry point (the reference's loop over mat_pad[:, :, i], utility.py:320-341):
-    # device-resident float32 planes at order 0 / 1 share ONE launch, the other cases go plane by plane inside it
+    if _spline_one_call(order, mat_pad.shape[2]) and mat_pad.shape[0] > 0 and mat_pad.shape[1] > 0:
+        return _spline_interleaved(mat_pad, (xcenter, ycenter, list_fact), None, order, mode, blend)
+    # more than four channels at orders 2..5, other blends at orders 0 / 1: channels as dense planes through the batched entry point
+    # (the reference's loop over mat_pad[:, :, i], utility.py:320-341): device-resident float32 planes at order 0 / 1 share ONE
+    # launch, the other cases go plane by plane inside it
     if is_torch:
         planes = mat_pad.permute(2, 0, 1).contiguous()
         out = _pp.unwarp_images_backward(planes, xcenter, ycenter, list_fact, order=order, mode=mode, blend=blend)

@@ -363,6 +363,31 @@ int dcp_unwarp_fused_color_image(const void* src, void* dst, int dtype, int64_t 
                                  int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact,
                                  const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream);
 
+/* The same three interleaved-pixel calls at spline orders 2..5 (the reference's examples/readthedocs_demo/demo_07.py:60 corrects a
+ * colour photograph channel by channel with order=3): every channel of the result is bit for bit what the single-plane spline
+ * entry point (dcp_unwarp_image_spline_f32 / _typed and their perspective and fused siblings) returns for that channel's
+ * column-strided view.  Arguments as dcp_unwarp_color_image / dcp_perspective_color_image / dcp_unwarp_fused_color_image with
+ * boundary_mode in place of blend_mode: DCP_MODE_* (0..7), optionally OR-ed with DCP_SPLINE_SCIPY_SUM.  Any DCP_DTYPE_*, order 2..5,
+ * channels 1..4, src_pixel_stride >= channels, rows that do not overlap; anything else is DCP_ERR_INVALID_ARG or
+ * DCP_ERR_UNSUPPORTED before any device call.  mem_kind: DCP_MEM_HOST or DCP_MEM_DEVICE (a call of several kernels cannot honour
+ * DCP_MEM_DEVICE_UNORDERED).  The single-plane prefilter runs once per channel, reading the channel in place, into a workspace of
+ * channels + 1 float64 planes; ONE gather follows, which evaluates a pixel's coordinate once for all its channels --
+ * spline_wg_color_kernel (the coefficient box of a 128 x 32 tile staged in LDS, channel after channel) under the level-2
+ * certificate of a radial or perspective map on frames of at least one tile, else spline_remap_color_kernel (one thread per pixel).
+ * Host memory: the interleaved extent goes up once, the dense (height, width, channels) result comes back once.  dcp_last_kernel
+ * reports the prefilter's kernels followed by "+ spline_wg_color_kernel<order=N, channels=C>" or
+ * "+ spline_remap_color_kernel<order=N, channels=C>".  Timings against the plane-by-plane route: not measured. */
+int dcp_unwarp_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels, int64_t src_row_stride,
+                                  int64_t src_pixel_stride, double xcenter, double ycenter, const double* list_fact, int nfact, int order,
+                                  int boundary_mode, int mem_kind, int device, void* stream);
+int dcp_perspective_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels,
+                                       int64_t src_row_stride, int64_t src_pixel_stride, const double* list_coef, int order, int boundary_mode,
+                                       int mem_kind, int device, void* stream);
+int dcp_unwarp_fused_color_image_spline(const void* src, void* dst, int dtype, int64_t height, int64_t width, int channels,
+                                        int64_t src_row_stride, int64_t src_pixel_stride, double xcenter, double ycenter,
+                                        const double* list_fact, int nfact, const double* list_coef, int order, int boundary_mode, int mem_kind,
+                                        int device, void* stream);
+
 /* ---- out-of-core stacks ----
  * The reference never touches more of a projection than mat3D[i, yd_min:yd_max, :]
  * (discorpy/post/postprocessing.py:221-228, 295-301), which is what lets it run on an HDF5 dataset

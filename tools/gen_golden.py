@@ -674,4 +674,34 @@ def g24():
 
 
 g24()
+
+
+# G25: a colour image at spline orders 2..5 through util.unwarp_color_image_backward (utility.py:278-342 loops map_coordinates over
+# mat_pad[:, :, i] with the caller's order and mode; examples/readthedocs_demo/demo_07.py:60 corrects a photograph with order=3).
+# G10's frame and calibration, float32 and uint8 pixels: float32 at orders 2..5 under reflect / nearest / grid-wrap, uint8 at order 3
+# under all eight modes, float32 at order 3 behind pad=4, pad_mode="edge".  Arrays only.
+def g25():
+    seed = 2510
+    rng = np.random.default_rng(seed)
+    rgb_f32 = rng.random((40, 56, 3), dtype=np.float32)
+    rgb_u8 = rng.integers(0, 255, (40, 56, 3), endpoint=True).astype(np.uint8)
+    xc, yc, fact = 27.4, 19.1, [1.0, 4e-3, 2e-5]
+    modes = ["reflect", "grid-mirror", "constant", "grid-constant", "nearest", "mirror", "grid-wrap", "wrap"]
+    out = dict(seed=np.int64(seed), shape=np.array(rgb_f32.shape), xcenter=f64(xc), ycenter=f64(yc), list_fact=f64(fact),
+               rgb_f32=rgb_f32, rgb_u8=rgb_u8)
+    for order in (2, 3, 4, 5):
+        for mode in ("reflect", "nearest", "grid-wrap"):
+            out["f32_o%d_%s" % (order, mode.replace("-", "_"))] = util.unwarp_color_image_backward(rgb_f32, xc, yc, fact, order=order, mode=mode)
+    for mode in modes:
+        out["u8_o3_%s" % mode.replace("-", "_")] = util.unwarp_color_image_backward(rgb_u8, xc, yc, fact, order=3, mode=mode)
+    out["f32_o3_reflect_pad_4_edge"] = util.unwarp_color_image_backward(rgb_f32, xc, yc, fact, order=3, mode="reflect", pad=4, pad_mode="edge")
+    for k, v in out.items():
+        if k.startswith("f32_"):
+            assert v.dtype == np.float32, k
+        if k.startswith("u8_"):
+            assert v.dtype == np.uint8 and v.shape == (40, 56, 3), k
+    save("g25_colour_spline40x56x3", **out)
+
+
+g25()
 print("done")

@@ -9,7 +9,16 @@ radial map (dcp_unwarp_fused_color_image) against NC single-plane calls on plane
 transposes a user of the single-plane functions also pays are not charged to them), the two ALTERNATING in one run: --rounds
 rounds of --reps launches each, median and range per side, the core clock under the colour kernel.
 
+--order N (2..5): the spline orders.  Side A is the one-call path of the three util functions (a prefilter per channel, one gather
+launch: dcp_*_color_image_spline), side B the plane-by-plane route the same functions took before it -- the channels as dense planes
+through post.unwarp_images_backward under the radial map, a loop of the single-plane function over mat[:, :, i] and a stack of the
+planes under the other two.  The two alternate in one process, --rounds rounds (at least five) of --reps calls each, synchronised host
+times per call; printed: the median and range of both sides, B's spread over its rounds, whether A is slower than B by more than
+that spread, whether the two outputs are equal, and the core clock under side A.  Cases: a device-resident --size x --size x 3
+float32 image under --map, and (--map radial) a host 3000 x 4000 x 3 uint8 NumPy image.
+
     python tools/time_color.py [--map radial|perspective|fused] [--size 4096] [--ring 6] [--reps 60] [--rounds 5] [--cases f32x3,f32x4,u8x3,u16x3]
+    python tools/time_color.py --order 3 [--map radial|perspective|fused] [--size 4096] [--reps 5] [--rounds 5] [--no-host]
 """
 import argparse
 import os
@@ -96,8 +105,102 @@ def ab_homography(a, L, dev):
             b.free()
 
 
+def ab_spline(a):
+    """--order 2..5: the one-call path (A) against the plane-by-plane route (B), alternating."""
+    import time
+    import torch
+    from discorpy_amd.post import postprocessing as pp
+    from discorpy_amd.util import utility as util
+    order, rounds = a.order, max(5, a.rounds)
+
+    def sync():
+        torch.cuda.synchronize()
+
+    def per_call(fn, reps):
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        sync()
+        return (time.perf_counter() - t0) / reps * 1e3, out
+
+    def alternate(tag, side_a, side_b, reps):
+        per_call(side_a, 1)
+        per_call(side_b, 1)                      # first use: workspace planes, output pool, clock ramp
+        ta, tb = [], []
+        for r in range(rounds):
+            t, out_a = per_call(side_a, reps)
+            ka = F.last_kernel()
+            ta.append(t)
+            t, out_b = per_call(side_b, reps)
+            kb = F.last_kernel()
+            tb.append(t)
+        same = bool(torch.equal(out_a, out_b)) if torch.is_tensor(out_a) else bool(np.array_equal(out_a, np.asarray(out_b)))
+        ma, mb, spread = float(np.median(ta)), float(np.median(tb)), max(tb) - min(tb)
+        print("%s order %d  A one call      %9.3f ms [%.3f .. %.3f]  %s" % (tag, order, ma, min(ta), max(ta), ka), flush=True)
+        print("%s order %d  B plane by plane %8.3f ms [%.3f .. %.3f]  spread %.3f ms  %s" % (tag, order, mb, min(tb), max(tb), spread, kb), flush=True)
+        print("%s order %d  A / B = %.3f   A - B = %+.3f ms against B's spread of %.3f ms: %s   outputs equal: %s" % (
+            tag, order, ma / mb, ma - mb, spread, "within the bar" if ma - mb <= spread else "MISSES the bar", same), flush=True)
+
+    size = a.size
+    s = size / 4096.0
+    if a.map == "radial":
+        cfg = configs.cfg2()
+        xc, yc, fact = cfg["xcenter"] * s, cfg["ycenter"] * s, [c * s ** -i for i, c in enumerate(cfg["list_fact"])]
+        coef = None
+    else:
+        cfg = configs.cfg3()
+        c = cfg["list_coef"]
+        coef = [c[0], c[1], c[2] * s, c[3], c[4], c[5] * s, c[6] / s, c[7] / s]
+        xc, yc, fact = cfg["xcenter"] * s, cfg["ycenter"] * s, [v * s ** -i for i, v in enumerate(cfg["list_fact"])]
+    rng = np.random.default_rng(3)
+    dev_img = torch.from_numpy(rng.random((size, size, 3), dtype=np.float32)).cuda()
+    for blend in (None, "scipy"):
+        if a.map == "radial":
+            def side_a():
+                return util.unwarp_color_image_backward(dev_img, xc, yc, fact, order=order, blend=blend)
+
+            def side_b():
+                planes = dev_img.permute(2, 0, 1).contiguous()
+                return pp.unwarp_images_backward(planes, xc, yc, fact, order=order, blend=blend).permute(1, 2, 0)
+        elif a.map == "perspective":
+            def side_a():
+                return util.correct_perspective_color_image(dev_img, coef, order=order, blend=blend)
+
+            def side_b():
+                return torch.stack([pp.correct_perspective_image(dev_img[:, :, i], coef, order=order, blend=blend) for i in range(3)], dim=2)
+        else:
+            def side_a():
+                return util.unwarp_perspective_fused_color_image(dev_img, xc, yc, fact, coef, order=order, blend=blend)
+
+            def side_b():
+                return torch.stack([pp.unwarp_perspective_fused(dev_img[:, :, i], xc, yc, fact, coef, order=order, blend=blend)
+                                    for i in range(3)], dim=2)
+        alternate("device %dx%dx3 f32 %-11s blend=%-5s" % (size, size, a.map, blend), side_a, side_b, a.reps)
+    clk = bench.clocks_under_load(side_a, sync)
+    print("clock under side A: %s" % (clk,), flush=True)
+    del dev_img
+    if a.map == "radial" and not a.no_host:
+        h, w = 3000, 4000                       # the reference's GoPro photograph (examples/readthedocs_demo/demo_07.py)
+        sh = w / 4096.0
+        cfg = configs.cfg2()
+        hxc, hyc, hfact = cfg["xcenter"] * sh, 0.5 * h, [c * sh ** -i for i, c in enumerate(cfg["list_fact"])]
+        photo = rng.integers(0, 255, (h, w, 3), endpoint=True).astype(np.uint8)
+
+        def host_a():
+            return util.unwarp_color_image_backward(photo, hxc, hyc, hfact, order=order)
+
+        def host_b():
+            planes = np.ascontiguousarray(np.moveaxis(photo, 2, 0))
+            return np.moveaxis(np.asarray(pp.unwarp_images_backward(planes, hxc, hyc, hfact, order=order)), 0, 2)
+        alternate("host %dx%dx3 u8 radial" % (h, w), host_a, host_b, max(1, a.reps // 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--order", type=int, default=1, choices=(1, 2, 3, 4, 5),
+                    help="2..5: the one-call spline path against the plane-by-plane route (see the module docstring)")
+    ap.add_argument("--no-host", action="store_true", help="--order 2..5: skip the host 3000 x 4000 x 3 uint8 case")
     ap.add_argument("--map", choices=("radial", "perspective", "fused"), default="radial")
     ap.add_argument("--rounds", type=int, default=5, help="--map perspective / fused: alternations of the two sides")
     ap.add_argument("--size", type=int, default=4096)
@@ -109,6 +212,8 @@ def main():
     L = F.lib()
     F.require_device()
     dev = -1
+    if a.order >= 2:
+        return ab_spline(a)
     if a.map != "radial":
         return ab_homography(a, L, dev)
     cfg = configs.cfg2()
