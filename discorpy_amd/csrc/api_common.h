@@ -24,7 +24,7 @@ const char* last_error();
     }                                                                                                      \
   } while (0)
 
-extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync;
+extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync, g_spline_frames;
 dcp::LaunchOpts current_opts();
 
 // Selects `device` for the calling thread for the lifetime of the object (no-op for device < 0).
@@ -153,8 +153,8 @@ static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPer
 // orders 0 / 1 on any element type (typed_kernels.hip, or remap_wg_kernel / the one-channel colour kernel where they qualify),
 // interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip), the forward scatter of any element
 // type (api_spline.cpp for its winner plane, forward_kernels.hip), interleaved channels at spline orders 2..5 (api_spline.cpp,
-// spline_color_kernels.hip).
-enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline, kExecForward, kExecColourSpline };
+// spline_color_kernels.hip), frames of one calibration at spline orders 2..5 (api_spline.cpp, spline_frames_kernels.hip).
+enum FrameExec : int { kExecTuned, kExecTyped, kExecColour, kExecSpline, kExecForward, kExecColourSpline, kExecFramesSpline };
 struct FrameCall {
   FrameExec exec;
   dcp::MapKind kind;
@@ -164,6 +164,7 @@ struct FrameCall {
   int dtype;
   int64_t H, W, rs, cs;            // strides in elements (interleaved channels: cs between pixels)
   int channels;                    // 1 except for interleaved channels
+  int64_t nframes = 1, fs = 0;     // kExecFramesSpline: frames of the call and their stride in elements
   const void* ycoord;              // kCoords: npts source coordinates, float32 or float64 (coord_dtype)
   const void* xcoord;
   int coord_dtype;
@@ -221,6 +222,9 @@ int run_spline(const FrameCall& c);
 // api_spline.cpp: interleaved channels at orders 2..5 (c.exec == kExecColourSpline; the device is selected): the single-plane prefilter
 // once per channel into a workspace slot of c.channels + 1 planes, then one gather launch
 int run_spline_color(const FrameCall& c);
+// api_spline.cpp: c.nframes frames of one calibration at orders 2..5 (c.exec == kExecFramesSpline; the device is selected), in groups of
+// up to "x_spline_frames" frames: the single-plane prefilter once per frame of a group, then one gather launch per group
+int run_spline_frames(const FrameCall& c);
 // api_spline.cpp: the forward-scatter executor (c.exec == kExecForward; the device is selected); its winner plane is leased from the
 // spline workspace
 int run_forward(const FrameCall& c);

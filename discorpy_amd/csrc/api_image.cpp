@@ -551,6 +551,7 @@ int run_frame(const FrameCall& c) {
   if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", c.device, hipGetErrorString(scope.status));
   if (c.exec == kExecSpline) return run_spline(c);
   if (c.exec == kExecColourSpline) return run_spline_color(c);
+  if (c.exec == kExecFramesSpline) return run_spline_frames(c);
   if (c.exec == kExecForward) return run_forward(c);
   if (!c.host) {
     DCP_HIP(launch_frame(c, c.src, c.dst, c.ycoord, c.xcoord, c.rs, c.cs, 0, 0, c.stream));
@@ -919,6 +920,34 @@ int dcp_unwarp_fused_color_image_spline(const void* src, void* dst, int dtype, i
                                  xcenter, ycenter, list_fact, nfact, list_coef, Points{}, order, DCP_BLEND_SCIPY, boundary_mode, 1, mem_kind,
                                  device, stream);
   return rc != DCP_OK ? rc : run_frame(c);
+}
+
+// Frames of one calibration at spline orders 2..5.  Every frame's result is that of the single-frame call on it, down to the homography's
+// division (see the colour entry points above: float32 divides plainly, the other element types as the typed entry point does).
+int dcp_remap_frames_spline(const void* src, void* dst, int dtype, int map_kind, int64_t nframes, int64_t height, int64_t width,
+                            int64_t frame_stride, int64_t row_stride, double xcenter, double ycenter, const double* list_fact,
+                            int nfact, const double* list_coef, int order, int mode, int mem_kind, int device, void* stream) {
+  if (map_kind != DCP_MAP_RADIAL && map_kind != DCP_MAP_PERSPECTIVE && map_kind != DCP_MAP_FUSED)
+    return fail(DCP_ERR_INVALID_ARG, "unknown map_kind %d", map_kind);
+  if (nframes < 0) return fail(DCP_ERR_INVALID_ARG, "nframes < 0");
+  if (nframes > 2147483647LL) return fail(DCP_ERR_UNSUPPORTED, "too many frames");
+  const dcp::MapKind kind = (dcp::MapKind)map_kind;
+  // (an empty stack checks everything but its pointers)
+  static const char nothing = 0;
+  const void* s = nframes == 0 && !src ? (const void*)&nothing : src;
+  void* d = nframes == 0 && !dst ? (void*)&nothing : dst;
+  FrameCall c;
+  const int rc = make_frame_call(&c, kExecFramesSpline, kind, s, d, dtype, height, width, row_stride, 1, 1, xcenter, ycenter, list_fact, nfact,
+                                 list_coef, Points{}, order, DCP_BLEND_SCIPY, mode, 1, mem_kind, device, stream);
+  if (rc != DCP_OK) return rc;
+  if (nframes > 1 && frame_stride < (height - 1) * row_stride + width)
+    return fail(DCP_ERR_INVALID_ARG, "frame stride %lld overlaps frames of %lld rows, %lld elements apart", (long long)frame_stride, (long long)height,
+                (long long)row_stride);
+  if (nframes == 0) return DCP_OK;
+  if (kind == dcp::kPersp && dtype == dcp::kF32) c.map.fast_div = 0;
+  c.nframes = nframes;
+  c.fs = nframes > 1 ? frame_stride : 0;
+  return run_frame(c);
 }
 
 int dcp_unwarp_image_forward(const void* src, void* dst, int dtype, int64_t height, int64_t width, int64_t src_row_stride,

@@ -1,5 +1,6 @@
 // api_spline.cpp -- spline orders 2..5 (scipy's prefiltered B-spline interpolation, spline_kernels.hip): the
-// per-device coefficient workspace and the spline executor of FrameCall (api_image.cpp holds the entry points).  The forward
+// per-device coefficient workspace and the spline executors of FrameCall -- one plane (run_spline), interleaved channels
+// (run_spline_color), frames of one calibration in groups (run_spline_frames); api_image.cpp holds the entry points.  The forward
 // scatter (forward_kernels.hip) leases its winner plane from the same workspace: run_forward.
 #include "api_common.h"
 
@@ -254,6 +255,65 @@ int run_spline_color(const FrameCall& c) {
     a.src = dsrc;
     return dcp::launch_spline_color(a, c.kind, c.map, c.channels, ddst, st);
   });
+}
+
+// c.nframes frames of one calibration (c.fs elements apart, unit column stride) at orders 2..5, in groups of G frames: the workspace slot
+// holds G + 1 planes -- the coefficients of every frame of a group and the prefilter's second plane --, per group the single-plane
+// prefilter runs once per frame and ONE gather launch follows, all on the call's stream.  G = min(frames left, option "x_spline_frames",
+// the largest G with (G + 1) planes <= 2 GiB), at least 1: the 2 GiB keep the two slots of a device at 4 GiB at most.  The slot is held
+// from the first group to the last.  Host memory: per group the source extent goes up once and the dense result comes back once.
+// "x_spline_frames" = 0: every frame through the single-frame executor (run_spline).
+int run_spline_frames(const FrameCall& c) {
+  hipStream_t st = c.stream;
+  const size_t esz = (size_t)dcp::elem_size(c.dtype);
+  const size_t frame_out = (size_t)c.H * (size_t)c.W * esz;
+  const int cap = g_spline_frames.load();
+  if (cap <= 0) {
+    FrameCall one = c;
+    one.exec = kExecSpline;
+    one.nframes = 1;
+    for (int64_t f = 0; f < c.nframes; ++f) {
+      one.src = (const char*)c.src + (size_t)f * (size_t)c.fs * esz;
+      one.dst = (char*)c.dst + (size_t)f * frame_out;
+      if (const int rc = run_spline(one)) return rc;
+    }
+    return DCP_OK;
+  }
+  dcp::SplineArgs a = spline_args_of(c);
+  const size_t plane_elems = (size_t)a.Hp * (size_t)a.Wp, plane = plane_elems * sizeof(double);
+  int64_t group = (int64_t)(((size_t)2 << 30) / plane) - 1;
+  if (group > cap) group = cap;
+  if (group > c.nframes) group = c.nframes;
+  if (group < 1) group = 1;
+  int cur_dev = 0;
+  DCP_HIP(hipGetDevice(&cur_dev));                           // (run_frame has selected it)
+  if (cur_dev < 0 || cur_dev >= 64) return fail(DCP_ERR_UNSUPPORTED, "device index %d", cur_dev);
+  SplineWorkspace::Slot* slot = nullptr;
+  DCP_HIP(g_spline_ws.acquire((size_t)(group + 1) * plane, st, cur_dev, &slot));
+  SlotGuard guard{slot, st};
+  a.coef = (double*)slot->buf;
+  for (int64_t f0 = 0; f0 < c.nframes; f0 += group) {
+    const int g = (int)(c.nframes - f0 < group ? c.nframes - f0 : group);
+    const char* gsrc = (const char*)c.src + (size_t)f0 * (size_t)c.fs * esz;
+    char* gdst = (char*)c.dst + (size_t)f0 * frame_out;
+    a.scratch = a.coef + (size_t)g * plane_elems;
+    if (!c.host) {
+      a.src = gsrc;
+      DCP_HIP(dcp::launch_spline_frames(a, c.kind, c.map, g, c.fs, gdst, st));
+      continue;
+    }
+    HostTrip t;
+    t.src = gsrc;
+    t.row_bytes = t.pitch = (size_t)((g - 1) * c.fs + (c.H - 1) * c.rs + c.W) * esz;
+    t.dst = gdst;
+    t.out_bytes = (size_t)g * frame_out;
+    const int rc = host_round_trip(t, st, [&](const void* dsrc, void* ddst, void*, void*) {
+      a.src = dsrc;
+      return dcp::launch_spline_frames(a, c.kind, c.map, g, c.fs, ddst, st);
+    });
+    if (rc != DCP_OK) return rc;
+  }
+  return DCP_OK;
 }
 
 // unwarp_image_forward: the winner plane (H W words) comes from the spline workspace -- a slot per stream, so calls on different streams

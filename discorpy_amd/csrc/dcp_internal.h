@@ -198,6 +198,7 @@ hipError_t read_bounds_unwarp(unsigned long long* out, bool reset);
 hipError_t read_bounds_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_color(unsigned long long* out, bool reset);
+hipError_t read_bounds_spline_frames(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -231,11 +232,15 @@ hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, 
 // spline_kernels.hip: the prefilter half of launch_spline -- the plane at a.src (strides a.src_stride / a.src_cstride) -> coefficients in
 // a.coef, a.scratch the second plane; `desc`: the kernels' names as dcp_last_kernel reports them in front of the gather's
 hipError_t launch_spline_prefilter(const SplineArgs& a, hipStream_t stream, char* desc, size_t desc_len);
-// does the LDS-staged gather (spline_wg_kernel / spline_wg_color_kernel) take this frame under this map?
+// does the LDS-staged gather (spline_wg_kernel / spline_wg_color_kernel / spline_wg_frames_kernel) take this frame under this map?
 bool spline_wg_takes(const SplineArgs& a, MapKind kind, const MapArgs& map);
 // spline_color_kernels.hip: interleaved (H, W, channels) image, channels = 1..4, radial / perspective / fused map, orders 2..5.
 // a.src_cstride = elements between pixels; a.coef = channels + 1 planes of Hp x Wp doubles (a.scratch is ignored); dst dense
 hipError_t launch_spline_color(const SplineArgs& a, MapKind kind, const MapArgs& map, int channels, void* dst, hipStream_t stream);
+// spline_frames_kernels.hip: `nframes` frames of one calibration, `src_frame_stride` elements apart (unit column stride), radial /
+// perspective / fused map, orders 2..5.  a.coef = nframes + 1 planes of Hp x Wp doubles (a.scratch is ignored); dst dense (nframes, H, W)
+hipError_t launch_spline_frames(const SplineArgs& a, MapKind kind, const MapArgs& map, int nframes, int64_t src_frame_stride, void* dst,
+                                hipStream_t stream);
 // typed_kernels.hip: any MapKind (kCoords: ca.npts points into img.dst)
 hipError_t launch_typed_image(MapKind kind, const TypedImageArgs& img, const MapArgs& map, const CoordArgs& ca,
                               hipStream_t stream);

@@ -661,6 +661,55 @@ def _per_frame(value, n, what):
     return vals
 
 
+def _stack_spline_one_call(kind, order, host):
+    """Does ``dcp_remap_frames_spline`` take a stack of frames under this map (F.MAP_*) at this spline order, from host or device
+    memory?  The one place that sends a case back to the frame-by-frame route.  Measured on the MI355X against that route (16 frames
+    of 4096 x 4096, float32 and uint16, ``tools/time_batch.py --order``, ``profiles/r09a_time_stack_spline.txt``): under the radial
+    map the one call is 4-5 % faster at order 3 and 8-14 % at order 5, under the homography 14-16 % faster at order 3 -- and SLOWER
+    at order 5 (1.6 x) and under the fused map (1.15 x at order 3, 1.3 x at order 5: the global gather of several coefficient planes
+    at once loses more in the caches than the shared coordinate saves).  Those cases keep the route; order 4 under the homography was
+    not measured and keeps it too."""
+    if not 2 <= order <= 5:
+        return False
+    if kind == F.MAP_RADIAL:
+        return True
+    if kind == F.MAP_PERSPECTIVE:
+        return order <= 3
+    return False
+
+
+def _frames_spline(kind, mats, xcenter, ycenter, fact, list_coef, order, mode, blend, out):
+    """The 3-D array `mats` (n, height, width) of ONE calibration at a spline order through ``dcp_remap_frames_spline`` -- NumPy or
+    device array of a real element type, unit column stride, frames that do not overlap, `out` None or a 3-D array --, or None
+    where the call has to go frame by frame."""
+    if not (hasattr(mats, "shape") and len(mats.shape) == 3 and mats.shape[0] >= 1):
+        return None
+    if out is not None and not (hasattr(out, "shape") and len(out.shape) == 3):
+        return None
+    if _is_torch(mats) or isinstance(mats, np.ndarray):
+        name = (mats.dtype.name if isinstance(mats, np.ndarray) else str(mats.dtype).replace("torch.", ""))
+    elif _is_cai(mats):
+        name = _cai_dtype(mats).name
+    else:
+        return None
+    if name not in F.DTYPE_BY_NAME or len(fact) > F.MAX_FACT:
+        return None
+    img = _Image(mats, 3)
+    if not _stack_spline_one_call(kind, order, img.mem == F.MEM_HOST):
+        return None
+    (n, height, width) = img.shape
+    ps, rs, cs = img.strides
+    if not (height >= 1 and width >= 1 and cs == 1 and rs >= width and (n == 1 or ps >= (height - 1) * rs + width)):
+        return None
+    fa, nf = F.fact_array(fact)
+    ca, _ = F.fact_array(_coefs(list_coef, "list_coef")) if list_coef is not None else (None, 0)
+    whole, optr = img.empty((n, height, width), out=out)
+    F.require_device()
+    F.check(F.lib().dcp_remap_frames_spline(img.ptr, optr, img.code, kind, n, height, width, ps, rs, float(xcenter), float(ycenter),
+                                            fa, nf, ca, order, _spline_mode(mode, blend), img.mem, img.device, img.stream))
+    return whole
+
+
 def unwarp_images_backward(mats, xcenter, ycenter, list_fact, order=1, mode="reflect", *, blend=None, out=None):
     """
     :func:`unwarp_image_backward` (reference ``postprocessing.py:111-148``) over a batch of images of one shape in ONE
@@ -682,7 +731,11 @@ def unwarp_images_backward(mats, xcenter, ycenter, list_fact, order=1, mode="ref
     list of 2D arrays (a sequence was given) or one 3D array (a 3D array was given); every image is bit-identical to what
     :func:`unwarp_image_backward` returns for it.  Device-resident float32 images at order 0 / 1 whose calibrations all
     hold the tile certificate go through ONE kernel launch per 55 images (``dcp_unwarp_images_f32``: the drain of one
-    frame overlaps the ramp of the next); anything else is processed image by image.
+    frame overlaps the ramp of the next).  A 3D array (NumPy or device) of a real element type under ONE calibration at
+    ``order >= 2`` goes to ``dcp_remap_frames_spline``: the frames are prefiltered one by one and gathered in groups by one
+    launch each, which evaluates a pixel's coordinate once for all frames of the group (``out=`` may be a 3D array and is
+    returned).  Anything else -- sequences of 2D arrays, per-image calibrations, complex input, column-strided or overlapping
+    views -- is processed image by image.
     """
     stacked = hasattr(mats, "shape") and len(mats.shape) == 3
     if hasattr(mats, "shape") and len(mats.shape) != 3:
@@ -702,6 +755,11 @@ def unwarp_images_backward(mats, xcenter, ycenter, list_fact, order=1, mode="ref
             raise ValueError("out must hold one array per image")
     if n == 0:
         return mats if stacked else []
+    # A (n, height, width) array of a real element type under ONE calibration at a spline order: one call (see _frames_spline)
+    if stacked and order >= 2 and not per_frame_fact and np.ndim(xcenter) == 0 and np.ndim(ycenter) == 0:
+        whole = _frames_spline(F.MAP_RADIAL, mats, xcs[0], ycs[0], facts[0], None, order, mode, blend, out)
+        if whole is not None:
+            return whole
     # A (n, height, width) DEVICE array of an integer type or float64 under ONE calibration, bilinear: the frames are the projections
     # of a stack whose every row is wanted -- the stack kernel on that element type (uint16: 0.59 of the HBM peak against 0.27
     # frame by frame), the same pixels (scipy's blend and store either way).  coord_round_f32 = 2 asks for unwarp_image_backward's
@@ -1168,7 +1226,8 @@ def unwarp_perspective_fused(mat, xcenter, ycenter, list_fact, list_coef, order=
 def _frames_under_map(kind, single, mats, xcenter, ycenter, list_fact, list_coef, order, mode, blend, out):
     """The frames `mats` (a sequence of 2-D arrays or one 3-D array) of one calibration under the homography (kind =
     F.MAP_PERSPECTIVE) or the fused map (F.MAP_FUSED): a 3-D device array the C ABI can address in place goes to
-    ``dcp_remap_frames_typed``, anything else frame by frame through ``single(frame, out)``."""
+    ``dcp_remap_frames_typed`` at orders 0 / 1, a 3-D device or NumPy array to ``dcp_remap_frames_spline`` at orders 2..5, anything
+    else frame by frame through ``single(frame, out)``."""
     if len(list_coef) != 8:
         raise ValueError("!!! Eight coefficients are required !!!")
     stacked = hasattr(mats, "shape") and len(mats.shape) == 3
@@ -1185,6 +1244,11 @@ def _frames_under_map(kind, single, mats, xcenter, ycenter, list_fact, list_coef
             raise ValueError("out must hold one array per image")
     if n == 0:
         return mats if stacked else []
+    # one call at the spline orders: a 3-D array, host or device (see _frames_spline)
+    if stacked and order >= 2:
+        whole = _frames_spline(kind, mats, xcenter, ycenter, _coefs(list_fact, "list_fact"), list_coef, order, mode, blend, out)
+        if whole is not None:
+            return whole
     # one call: a 3-D DEVICE array of a real element type, orders 0 / 1, unit column stride, frames that do not overlap (the library
     # itself falls back to the single-frame kernels where its one-launch kernel does not apply: the same bits either way)
     if (stacked and order <= 1 and (out is None or out3) and (_is_torch(mats) and mats.is_cuda or _is_cai(mats))
@@ -1230,7 +1294,9 @@ def correct_perspective_images(mats, list_coef, order=1, mode="reflect", *, blen
     bit-identical to what :func:`correct_perspective_image` returns for it under the same ``blend``.  A 3D device array
     with unit column stride and non-overlapping frames goes to ``dcp_remap_frames_typed``: float32, uint8 and uint16 at
     order 1 under a certified homography run in one kernel launch (the coordinates of a tile are evaluated once for all
-    frames); anything else is processed frame by frame.
+    frames).  At ``order >= 2`` a 3D array, NumPy or device, goes to ``dcp_remap_frames_spline``: one prefilter per frame,
+    then one gather launch per group of frames with the coordinates evaluated once for the group.  Anything else is
+    processed frame by frame.
     """
     return _frames_under_map(F.MAP_PERSPECTIVE, lambda f, o: correct_perspective_image(f, list_coef, order, mode, blend=blend, out=o),
                              mats, 0.0, 0.0, [], list_coef, order, mode, blend, out)

@@ -377,10 +377,21 @@ def unwarp_color_image_backward(mat, xcenter, ycenter, list_fact, order=1, mode=
     # more than four channels at orders 2..5, other blends at orders 0 / 1: channels as dense planes through the batched entry point
     # (the reference's loop over mat_pad[:, :, i], utility.py:320-341): device-resident float32 planes at order 0 / 1 share ONE
     # launch, the other cases go plane by plane inside it
+    # (at orders 2..5 the planes are handed over as a SEQUENCE: this route stays plane by plane, as it was before a 3-D array at a
+    # spline order became one call of dcp_remap_frames_spline in post.unwarp_images_backward)
     if is_torch:
         planes = mat_pad.permute(2, 0, 1).contiguous()
-        out = _pp.unwarp_images_backward(planes, xcenter, ycenter, list_fact, order=order, mode=mode, blend=blend)
+        if order >= 2 and planes.shape[0] > 0:
+            import torch
+            out = torch.stack(_pp.unwarp_images_backward([planes[i] for i in range(planes.shape[0])], xcenter, ycenter, list_fact, order=order,
+                                                         mode=mode, blend=blend))
+        else:
+            out = _pp.unwarp_images_backward(planes, xcenter, ycenter, list_fact, order=order, mode=mode, blend=blend)
         return out.permute(1, 2, 0)
     planes = np.ascontiguousarray(np.moveaxis(mat_pad, 2, 0))
-    mat_corr = _pp.unwarp_images_backward(planes, xcenter, ycenter, list_fact, order=order, mode=mode, blend=blend)
+    if order >= 2 and planes.shape[0] > 0:
+        mat_corr = np.stack(_pp.unwarp_images_backward([planes[i] for i in range(planes.shape[0])], xcenter, ycenter, list_fact, order=order,
+                                                       mode=mode, blend=blend))
+    else:
+        mat_corr = _pp.unwarp_images_backward(planes, xcenter, ycenter, list_fact, order=order, mode=mode, blend=blend)
     return np.moveaxis(np.asarray(mat_corr), 0, 2)

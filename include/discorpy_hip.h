@@ -436,6 +436,27 @@ int dcp_remap_frames_typed(const void* src, void* dst, int dtype, int map_kind, 
                            int64_t frame_stride, int64_t row_stride, double xcenter, double ycenter, const double* list_fact,
                            int nfact, const double* list_coef, int order, int blend_mode, int mem_kind, int device, void* stream);
 
+/* `nframes` frames of ONE calibration at spline orders 2..5 -- the loop a caller writes around unwarp_image_backward(frame, ..., order=3)
+ * (discorpy/post/postprocessing.py:111-148; examples/readthedocs_demo/demo_07.py:25,60 per frame of a series), around
+ * correct_perspective_image (:444-459, 462-492) or around both corrections (demo_05.py:127,147) -- with ONE evaluation of a pixel's
+ * source coordinate for all frames of a launch.  Every frame of the result is bit for bit what the single-frame spline entry point
+ * (dcp_unwarp_image_spline_f32 / dcp_unwarp_image_typed and their perspective and fused siblings) returns for it.
+ *   map_kind  DCP_MAP_RADIAL, DCP_MAP_PERSPECTIVE or DCP_MAP_FUSED; arguments the map does not use are ignored and may be null
+ *   src       frames `frame_stride` elements apart (not overlapping, unless nframes = 1), rows `row_stride` elements apart, unit column stride
+ *   dst       dense (nframes, height, width), elements of `dtype` (any DCP_DTYPE_*) like the source
+ *   order     2..5;  mode: DCP_MODE_* (0..7), optionally OR-ed with DCP_SPLINE_SCIPY_SUM
+ *   mem_kind  DCP_MEM_HOST or DCP_MEM_DEVICE
+ * Anything else is DCP_ERR_INVALID_ARG or DCP_ERR_UNSUPPORTED before any device call; nframes = 0 is DCP_OK with no launch.  The frames
+ * are processed in groups: per group the single-plane prefilter runs once per frame, reading the frame in place, into a workspace of
+ * (frames of the group + 1) float64 planes of at most 2 GiB, and ONE gather follows -- spline_wg_frames_kernel (the coefficient box of a
+ * 128 x 32 tile staged in LDS, frame after frame) under the level-2 certificate of a radial or perspective map on frames of at least
+ * one tile, else spline_remap_frames_kernel (one thread per pixel).  Host memory: per group the source extent goes up once and the
+ * dense result comes back once.  dcp_debug_last_kernel() reports the last group's prefilter kernels followed by
+ * "+ spline_wg_frames_kernel<order=N, frames=G>" or "+ spline_remap_frames_kernel<order=N, frames=G>". */
+int dcp_remap_frames_spline(const void* src, void* dst, int dtype, int map_kind, int64_t nframes, int64_t height, int64_t width,
+                            int64_t frame_stride, int64_t row_stride, double xcenter, double ycenter, const double* list_fact,
+                            int nfact, const double* list_coef, int order, int mode, int mem_kind, int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the
