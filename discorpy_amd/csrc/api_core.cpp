@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) {
 
 const char* last_error() { return g_err; }
 
-std::atomic<int> g_tile_rows{16}, g_xcd_remap{2}, g_coef_lds{0}, g_d_chunk{16}, g_pipe_depth{2}, g_lds_gather{1}, g_stack_chunk_kb{24576}, g_stack_lds{1}, g_host_duplex{1}, g_host_bands{6}, g_tile_cert{1}, g_wg_box{1}, g_wg_per_cu{0}, g_stack_wg{1}, g_int_exact{1}, g_host_direct{1}, g_tall_tiles{0}, g_store_wait{1}, g_fused_wg{1}, g_any_order{0}, g_host_band_sync{0}, g_spline_frames{8};
+std::atomic<int> g_tile_rows{16}, g_xcd_remap{2}, g_coef_lds{0}, g_d_chunk{16}, g_pipe_depth{2}, g_lds_gather{1}, g_stack_chunk_kb{24576}, g_stack_lds{1}, g_host_duplex{1}, g_host_bands{6}, g_tile_cert{1}, g_wg_box{1}, g_wg_per_cu{0}, g_stack_wg{1}, g_int_exact{1}, g_host_direct{1}, g_tall_tiles{0}, g_store_wait{1}, g_fused_wg{1}, g_any_order{0}, g_host_band_sync{0}, g_spline_frames{8}, g_median_lds{1};
 
 dcp::LaunchOpts current_opts() {
   dcp::LaunchOpts o;
@@ -644,6 +644,8 @@ int dcp_set_option(const char* key_in, int value) {
     if (value < 0 || value > 16) return fail(DCP_ERR_INVALID_ARG, "spline_frames must be in [0, 16]");
     g_spline_frames = value;          // dcp_remap_frames_spline: frames per gather launch (the workspace holds that many coefficient planes + 1); 0: frame by frame
                                       // through the single-frame executor (A/B and parity runs)
+  } else if (!strcmp(key, "median_lds")) {
+    g_median_lds = value ? 1 : 0;     // 0: dcp_median_filter_2d reads every tap from global memory (median_global_kernel) even where a key box fits LDS
   } else if (!strcmp(key, "tile_cert")) {
     g_tile_cert = value ? 1 : 0;      // 0: never use the host's tile-deviation certificate (remap_lds_kernel then votes)
   } else if (!strcmp(key, "stack_chunk_kb")) {
@@ -680,6 +682,7 @@ int dcp_get_option(const char* key_in, int* value) {
   else if (!strcmp(key, "spline_xcd")) *value = dcp::get_spline_xcd();
   else if (!strcmp(key, "spline_wg")) *value = dcp::get_spline_wg();
   else if (!strcmp(key, "spline_frames")) *value = g_spline_frames;
+  else if (!strcmp(key, "median_lds")) *value = g_median_lds;
   else if (!strcmp(key, "box_table")) *value = dcp::get_box_table();
   else if (!strcmp(key, "frame_plan")) *value = dcp::get_frame_plan();
   else if (!strcmp(key, "frame_plan_tiles") || !strcmp(key, "frame_plan_exact_tiles")) {

@@ -265,6 +265,11 @@ struct ForwardArgs {
   int32_t esize;
 };
 hipError_t launch_forward(const ForwardArgs& a, const MapArgs& map, hipStream_t stream);
+// median_kernels.hip: the size_y x size_x median (rank size_y size_x / 2) of every pixel's window under scipy's "reflect", any ElemType;
+// rows of src `src_stride` elements apart, dst dense, the two not overlapping.  use_lds = false: every tap from global memory
+// (median_global_kernel) even where a key box fits LDS (median_lds_kernel)
+hipError_t launch_median(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, int size_y, int size_x, bool use_lds,
+                         hipStream_t stream);
 // interleaved (H, W, C) image, radial / perspective / fused map, orders 0 / 1; src_cstride = elements between pixels
 hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
 // color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, level-2 certificate of
