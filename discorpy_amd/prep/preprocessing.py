@@ -15,8 +15,10 @@ current stream) or ``__cuda_array_interface__`` device arrays, as in :mod:`disco
 
 Where this differs from scipy:
 
-* NaN input gives an undefined result, as it does in scipy (there the outcome depends on where the NaNs sit in the window);
-* ``-0.0`` and ``+0.0`` are equal in value and either may come out (here ``-0.0`` sorts below ``+0.0``);
+* floats are selected in IEEE 754 total order, so the result is defined bit for bit: ``-0.0`` sorts below ``+0.0`` (scipy treats them
+  as equal and either may come out of it), negative NaNs sort below ``-inf`` and positive NaNs above ``+inf``, each by payload (in
+  scipy the outcome depends on where the NaNs sit in the window).  A NaN counts as one element of the windows that hold it and
+  touches no other pixel;
 * 64-bit integers are selected exactly; scipy passes them through a double, so values beyond 2**53 may differ from it;
 * the window is reflected with period ``2 n`` for any number of folds, so an image may be much smaller than the window.  scipy
   1.15.3 does not reflect correctly once half the window reaches ``4 * side`` on a side longer than 1 (e.g. a 3 x 40 image at size
