@@ -24,7 +24,7 @@ const char* last_error();
     }                                                                                                      \
   } while (0)
 
-extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync, g_spline_frames, g_median_lds;
+extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync, g_spline_frames, g_median_lds, g_gauss_lds;
 dcp::LaunchOpts current_opts();
 
 // Selects `device` for the calling thread for the lifetime of the object (no-op for device < 0).
@@ -145,6 +145,16 @@ int frames_as_stack(const float* src0, float* dst0, int nframes, int64_t height,
 
 // api_spline.cpp: frees the coefficient planes of every device (waits for the devices first)
 int release_spline_workspace();
+
+// api_spline.cpp: `bytes` of the spline workspace of the current device for a call on `st` (a slot per stream, ordered behind the slot's
+// previous use on the device), held until the lease goes out of scope -- after the call's last kernel has been enqueued
+struct WorkspaceLease {
+  void* buf = nullptr;
+  void* slot = nullptr;
+  hipStream_t st = nullptr;
+  int acquire(size_t bytes, hipStream_t stream);
+  ~WorkspaceLease();
+};
 
 static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPersp && DCP_MAP_FUSED == dcp::kFused, "map kinds");
 

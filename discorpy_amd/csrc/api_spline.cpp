@@ -156,6 +156,22 @@ int release_spline_workspace() {
   return DCP_OK;
 }
 
+int WorkspaceLease::acquire(size_t bytes, hipStream_t stream) {
+  int cur_dev = 0;
+  DCP_HIP(hipGetDevice(&cur_dev));
+  if (cur_dev < 0 || cur_dev >= 64) return fail(DCP_ERR_UNSUPPORTED, "device index %d", cur_dev);
+  SplineWorkspace::Slot* s = nullptr;
+  DCP_HIP(g_spline_ws.acquire(bytes, stream, cur_dev, &s));
+  slot = s;
+  buf = s->buf;
+  st = stream;
+  return DCP_OK;
+}
+
+WorkspaceLease::~WorkspaceLease() {
+  if (slot) g_spline_ws.release(static_cast<SplineWorkspace::Slot*>(slot), st);
+}
+
 // The SplineArgs of a validated spline call, all but the workspace planes and the source pointer.
 static dcp::SplineArgs spline_args_of(const FrameCall& c) {
   dcp::SplineArgs a;

@@ -199,6 +199,7 @@ hipError_t read_bounds_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_frames(unsigned long long* out, bool reset);
+hipError_t read_bounds_gauss(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -270,6 +271,18 @@ hipError_t launch_forward(const ForwardArgs& a, const MapArgs& map, hipStream_t 
 // (median_global_kernel) even where a key box fits LDS (median_lds_kernel)
 hipError_t launch_median(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, int size_y, int size_x, bool use_lds,
                          hipStream_t stream);
+// gauss_kernels.hip: the symmetric correlation of scipy.ndimage.gaussian_filter, axis 0 (weights wy, radius ry) then axis 1 (wx, rx) on the
+// result rounded to the element type; w*: 2 r + 1 host doubles, symmetric (only the first r + 1 are read); a radius of -1 skips its
+// axis (both: a copy).  `boundary` is a BoundaryMode (the grid- spellings are scipy's aliases here), cval the value outside under
+// kModeConstant.  Rows of src `src_stride` elements apart, dst dense, the two not overlapping.  One launch (gauss_lds_kernel) where
+// gauss_takes_lds() says so, else one launch of gauss_axis_kernel per axis; with both axes that route writes the first pass to `tmp`
+// (H W elements of the type, device memory; unused and may be null otherwise).  Any ElemType but kBool.
+constexpr int kGaussMaxRadius = 192;     // the weights travel in the kernels' argument block: 2 x 193 doubles
+constexpr int kGaussFusedMaxRadius = 24; // "x_gauss_lds" = 1: gauss_lds_kernel is the default up to this radius and
+constexpr int kGaussFusedMaxLds = 80 << 10;  // this many bytes of LDS, two workgroups per CU (see gauss_takes_lds)
+bool gauss_takes_lds(int dtype, int ry, int rx, int lds_mode);
+hipError_t launch_gauss(const void* src, void* dst, void* tmp, int H, int W, int64_t src_stride, int dtype, const double* wy, int ry,
+                        const double* wx, int rx, int boundary, double cval, int lds_mode, hipStream_t stream);
 // interleaved (H, W, C) image, radial / perspective / fused map, orders 0 / 1; src_cstride = elements between pixels
 hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
 // color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, level-2 certificate of

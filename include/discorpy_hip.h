@@ -475,6 +475,30 @@ int dcp_remap_frames_spline(const void* src, void* dst, int dtype, int map_kind,
 int dcp_median_filter_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, int size_y, int size_x,
                          int mem_kind, int device, void* stream);
 
+/* ---- line and chessboard patterns: the Gaussian filter ----
+ * discorpy/prep/linepattern.py:592,659,739 (scipy.ndimage.gaussian_filter): a symmetric 1-D correlation along axis 0 (weights_y, radius_y),
+ * then along axis 1 (weights_x, radius_x) of the first pass's result ROUNDED TO THE ELEMENT TYPE, with scipy's arithmetic bit for bit.
+ * One element of one pass, e the extended line read as doubles, w the 2 r + 1 weights:
+ *     tmp = e[i] * w[r];   for j = -r .. -1:  tmp += (e[i + j] + e[i - j]) * w[r + j];      (float64, no fused multiply-add)
+ * then a C cast to the element type (floats round to nearest, integers truncate toward zero; 64-bit integers are read through a
+ * double; defined where the double lies within the type's range).  Position p of a line of length n, any integer p, under `mode`
+ * (a DCP_MODE_*): REFLECT / GRID_MIRROR  q = p mod 2 n, 2 n - 1 - q where q >= n;  MIRROR  index 0 if n == 1, else q = p mod (2 n - 2),
+ * 2 n - 2 - q where q >= n;  NEAREST  clipped;  WRAP / GRID_WRAP  p mod n;  CONSTANT / GRID_CONSTANT  the double `cval`, not cast to
+ * the element type (in the second pass a column outside the image is cval too, not a filtered value).
+ *   weights_*  HOST pointers to 2 * radius + 1 doubles, symmetric to the bit; NULL or radius -1 skips the axis (both: dst = src);
+ *              radius <= 192 (sigma 48 at scipy's truncate = 4)
+ *   src   rows `src_row_stride` elements apart (>= width), unit column stride;  dst  dense (height, width), not overlapping src
+ *   dtype any DCP_DTYPE_* but BOOL;  mem_kind  DCP_MEM_HOST (staged up and down by the library) or DCP_MEM_DEVICE (enqueued on `stream`)
+ * Asymmetric weights, a height or width below 1, a stride below the width, a radius below -1, an unknown dtype, mode or mem_kind and
+ * overlapping buffers are DCP_ERR_INVALID_ARG, DCP_DTYPE_BOOL and a radius above 192 are DCP_ERR_UNSUPPORTED, all before any device
+ * call.  One launch of gauss_lds_kernel (the source box of a 128 x 32 tile and the first pass's plane both in LDS) where both axes are
+ * filtered with radii up to 24 and the planes take at most 80 KiB -- the range in which it measured no slower: 0.30 against 0.41 ms for a
+ * device-resident 4096 x 4096 float32 image at sigma 3 --, else one launch of gauss_axis_kernel per axis (taps from global memory, the plane between the passes in the
+ * library's scratch: dcp_release_scratch frees it; 1.05 ms at sigma 10); dcp_debug_last_kernel() names what ran. */
+int dcp_correlate_sym_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype,
+                         const double* weights_y, int radius_y, const double* weights_x, int radius_x,
+                         int mode, double cval, int mem_kind, int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the
