@@ -115,6 +115,9 @@ SIGNATURES = {
                                        _int, _vp]),
     "dcp_median_filter_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _int, _vp]),
     "dcp_correlate_sym_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _dp, _int, _dp, _int, _int, _dbl, _int, _int, _vp]),
+    "dcp_label_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, C.POINTER(_int), _int, _int, _vp]),
+    "dcp_label_measures_2d": (_int, [_vp, _vp, _int, _int, C.c_long, C.c_long, _int, _int, _vp, _vp, _int, _int, _vp]),
+    "dcp_fill_holes_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
     "dcp_debug_counters": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_bounds": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_last_kernel": (C.c_char_p, []),

@@ -200,6 +200,7 @@ hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_frames(unsigned long long* out, bool reset);
 hipError_t read_bounds_gauss(unsigned long long* out, bool reset);
+hipError_t read_bounds_label(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -283,6 +284,23 @@ constexpr int kGaussFusedMaxLds = 80 << 10;  // this many bytes of LDS, two work
 bool gauss_takes_lds(int dtype, int ry, int rx, int lds_mode);
 hipError_t launch_gauss(const void* src, void* dst, void* tmp, int H, int W, int64_t src_stride, int dtype, const double* wy, int ry,
                         const double* wx, int rx, int boundary, double cval, int lds_mode, hipStream_t stream);
+// label_kernels.hip: connected components of the nonzero pixels (any ElemType; floats by their bits: NaN is set, -0.0 is not) numbered
+// as scipy.ndimage.label numbers them, into dst (dense H x W int32, 0 = background).  conn8: the full 3 x 3 structure, else the cross.
+// `parent`: H W int32 of device scratch, `counts`: label_count_words(H, W) more; the number of labels is left in the LAST word of
+// counts.  use_lds = false: no tile-local stage, the global union over every pixel pair (option "x_label_lds" = 0).  H W < 2^31.
+constexpr int kLabelTW = 128, kLabelTH = 32;   // label_tile_kernel's tile: kLabelTW * kLabelTH int32 = 16 KiB of LDS
+constexpr int kLabelScanChunk = 4096;          // pixels per workgroup of the root count and rank
+size_t label_count_words(int H, int W);
+hipError_t launch_label(const void* src, int32_t* dst, int32_t* parent, int32_t* counts, int H, int W, int64_t src_stride, int dtype, bool conn8,
+                        bool use_lds, hipStream_t stream);
+// scipy.ndimage.binary_fill_holes into dst (dense H x W bytes of 0 / 1); `parent` and `root`: H W int32 of device scratch each
+hipError_t launch_fill_holes(const void* src, uint8_t* dst, int32_t* parent, int32_t* root, int H, int W, int64_t src_stride, int dtype,
+                             bool use_lds, hipStream_t stream);
+// per label 1..num of `labels` (rows l_stride apart; other values are ignored): sums[num][4] = pixel count, sum v, sum y v, sum x v over
+// its pixels and boxes[num][4] = min y, max y, min x, max x ((H, -1, W, -1) for an absent label); v from `weights` (kBool, kU8, kI8, kU16
+// or kI16; rows w_stride apart) or 1 everywhere where weights is null
+hipError_t launch_label_measures(const void* weights, const int32_t* labels, int H, int W, int64_t w_stride, int64_t l_stride, int dtype, int num,
+                                 long long* sums, int32_t* boxes, hipStream_t stream);
 // interleaved (H, W, C) image, radial / perspective / fused map, orders 0 / 1; src_cstride = elements between pixels
 hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
 // color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, level-2 certificate of

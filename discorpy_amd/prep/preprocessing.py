@@ -1,11 +1,16 @@
-"""MI355X counterpart of the median-filter part of ``discorpy.prep.preprocessing``.
+"""MI355X counterpart of the ``scipy.ndimage`` part of ``discorpy.prep.preprocessing``: the median filter and the dot-pattern route.
 
 * :func:`normalization`   reference ``discorpy/prep/preprocessing.py:50-73``: same name, arguments and default
 * :func:`median_filter`   the ``scipy.ndimage.median_filter(mat, size, mode="reflect")`` both :func:`normalization` (size 51) and the
-  denoise step of the reference's ``binarization`` (size 2) rest on -- the one expensive image operation of that module
+  denoise step of the reference's ``binarization`` (size 2) rest on
+* :func:`label`, :func:`sum_labels`, :func:`center_of_mass`, :func:`find_objects`, :func:`binary_fill_holes`   the ``scipy.ndimage``
+  functions of those names the reference calls on binary dot images (``preprocessing.py:247-445``, ``:966-997``), equal to scipy's
+  results element for element
+* :func:`check_num_dots`, :func:`get_points_dot_pattern` (``binarize=False``), :func:`select_dots_based_size`,
+  :func:`select_dots_based_distance`   the reference's functions on top of them: same names, arguments, messages and prints
 
-The rest of the reference's module (Otsu threshold, ``clear_border``, morphology, labelling, the Radon-based angle search) rests on
-scikit-image and is out of scope here: there is nothing to compare an implementation against.
+The rest of the reference's module (Otsu threshold, ``clear_border``, morphology and ``regionprops``, the Radon-based angle search)
+rests on scikit-image and is out of scope here: there is nothing to compare an implementation against.
 
 The median runs as a hand-written HIP kernel through ``dcp_median_filter_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/median_kernels.hip``): it SELECTS the element of rank ``(size_y * size_x) // 2`` of every window by a binary search on
@@ -13,7 +18,15 @@ order-preserving integer keys, so the result is one of the input's elements, bit
 path: a missing library or GPU raises.  Inputs are NumPy arrays (staged through the GPU), ROCm torch tensors (zero-copy, on torch's
 current stream) or ``__cuda_array_interface__`` device arrays, as in :mod:`discorpy_amd.post.postprocessing`.
 
-Where this differs from scipy:
+Labelling (``dcp_label_2d``, ``csrc/label_kernels.hip``) is a union-find whose roots are the components' smallest linear indices: a
+tile per workgroup in LDS, the tile seams by atomic min on a parent plane, then a prefix sum over the root flags, which numbers the
+components in the raster order of their first pixels -- scipy's numbering, without a sort or a host pass.  The measurements
+(``dcp_label_measures_2d``) are int64 sums and 32-bit boxes accumulated with integer atomics, exact in any order; the quotients are
+formed in NumPy float64 as scipy forms them, so for bool and 8- / 16-bit integer images (every partial sum an integer below 2**53)
+they equal scipy's bit for bit.  Float and wider integer weights raise ``NotImplementedError``: the reference only ever measures
+binary images.  :func:`binary_fill_holes` is the same labelling run on the complement (4-neighbour structure) plus a border flag.
+
+Where the median differs from scipy:
 
 * floats are selected in IEEE 754 total order, so the result is defined bit for bit: ``-0.0`` sorts below ``+0.0`` (scipy treats them
   as equal and either may come out of it), negative NaNs sort below ``-inf`` and positive NaNs above ``+inf``, each by payload (in
@@ -27,6 +40,7 @@ Where this differs from scipy:
   supported")`` as everywhere in this package (scipy's median filter itself accepts float16);
 * only 2-D input is taken.
 """
+import ctypes
 import operator
 
 import numpy as np
@@ -35,6 +49,9 @@ from .. import _ffi as F
 from ..post.postprocessing import _Image, _is_cai, _is_torch
 
 __all__ = ["normalization", "median_filter"]
+# the dot-pattern route (labelling, measurements, hole filling and the reference's functions on top of them)
+DOT_PATTERN = ["label", "sum_labels", "center_of_mass", "find_objects", "binary_fill_holes", "check_num_dots", "get_points_dot_pattern",
+               "select_dots_based_size", "select_dots_based_distance"]
 
 
 def _window(size):
@@ -131,3 +148,388 @@ def normalization(mat, size=51):
         mat_bck[mat_bck == 0.0] = mean_val
         mat_cor = mean_val * mat / mat_bck
     return mat_cor
+
+
+# --------------------------------------------------------------------------- the dot-pattern route
+
+_CROSS = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
+_MEASURED = ("bool", "uint8", "int8", "uint16", "int16")
+
+
+def _rows_image(mat):
+    """``mat`` as a 2-D :class:`_Image` with unit column stride and non-overlapping rows (a copy where it is not)."""
+    img = _Image(mat, 2)
+    if img.strides[1] != 1 and img.shape[1] > 1 or img.strides[0] < img.shape[1] and img.shape[0] > 1:
+        if img.cai:
+            raise ValueError("device arrays must have unit column stride and non-overlapping rows")
+        img = _Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 2)
+    return img
+
+
+def _row_stride(img):
+    return img.strides[0] if img.shape[0] > 1 else img.shape[1]          # (a single row's stride is arbitrary)
+
+
+def _new_like(img, shape, dtype):
+    """(array, pointer): a fresh C-contiguous array of NumPy dtype ``dtype`` and of the kind of ``img``."""
+    if img.torch:
+        import torch
+        out = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=img.keep.device)
+        return out, out.data_ptr()
+    if img.cai:
+        out = F.DeviceArray(shape, dtype, img.device)
+        return out, out.ptr
+    out = np.empty(shape, dtype)
+    return out, out.ctypes.data
+
+
+def _to_host(img, arr):
+    """NumPy copy of ``arr``, an array :func:`_new_like` made for ``img`` (after the work enqueued on the image's stream)."""
+    if img.torch:
+        return arr.cpu().numpy()
+    if img.cai:
+        F.check(F.lib().dcp_stream_synchronize(img.device, img.stream))
+        return arr.copy_to_host()
+    return arr
+
+
+def _connectivity(structure):
+    """4 or 8 for ``structure`` = None, the 3 x 3 cross or the 3 x 3 block (compared by value)."""
+    if structure is None:
+        return 4
+    st = np.asarray(structure, dtype=bool)
+    if st.ndim != 2:
+        raise RuntimeError("structure and input must have equal rank")          # scipy's words
+    if st.shape != (3, 3):
+        raise ValueError("structure dimensions must be equal to 3")             # scipy's words
+    if np.array_equal(st, _CROSS):
+        return 4
+    if st.all():
+        return 8
+    raise NotImplementedError("structure must be None, the 3 x 3 cross or the full 3 x 3 block")
+
+
+def label(mat, structure=None):
+    """
+    Label the connected components of the nonzero pixels: ``scipy.ndimage.label(mat, structure)`` on the GPU.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array (NumPy array, ROCm torch tensor or ``__cuda_array_interface__`` device array) of any real element type.  A pixel
+        is set where it is nonzero (NaN is, ``-0.0`` is not).  A view whose rows are strided is read in place.
+    structure : array_like, optional
+        None or the 3 x 3 cross (4-connectivity), or the full 3 x 3 block (8-connectivity).
+
+    Returns
+    -------
+    labels : array_like
+        2D int32 array of the input's kind: 0 for background, 1..num numbered as scipy numbers them.
+    num : int
+        Number of components.
+    """
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    conn = _connectivity(structure)
+    img = _rows_image(mat)
+    height, width = img.shape
+    labels, lptr = _new_like(img, (height, width), np.int32)
+    if height == 0 or width == 0:
+        return labels, 0
+    F.require_device()
+    num = ctypes.c_int(0)
+    F.check(F.lib().dcp_label_2d(img.ptr, lptr, height, width, _row_stride(img), img.code, conn, ctypes.byref(num), img.mem, img.device,
+                                 img.stream))
+    return labels, int(num.value)
+
+
+def binary_fill_holes(mat):
+    """
+    Fill the holes of the nonzero pixels: ``scipy.ndimage.binary_fill_holes(mat)`` (default structure) on the GPU.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array of any real element type, as for :func:`label`.
+
+    Returns
+    -------
+    array_like
+        2D bool array of the input's kind: the nonzero pixels and every region of zeros that reaches no border through its
+        4-neighbours.
+    """
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    img = _rows_image(mat)
+    height, width = img.shape
+    res, rptr = _new_like(img, (height, width), np.bool_)
+    if height == 0 or width == 0:
+        return res
+    F.require_device()
+    F.check(F.lib().dcp_fill_holes_2d(img.ptr, rptr, height, width, _row_stride(img), img.code, img.mem, img.device, img.stream))
+    return res
+
+
+def _is_device(a):
+    return (_is_torch(a) and a.is_cuda) or _is_cai(a)
+
+
+_WIDE_LABELS = "labels outside the int32 range are not implemented: the kernels' labels are int32 (scipy's own label type)"
+
+
+def _int32_labels(labels):
+    """``labels`` as int32, read in place where it is; a wider plane is converted after a check that no value would wrap."""
+    lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
+    if _is_torch(labels):
+        import torch
+        if labels.dtype == torch.int32:
+            return labels
+        if labels.is_floating_point() or labels.is_complex():
+            raise TypeError("labels must be integers")
+        if labels.element_size() >= 4 and labels.numel() and (int(labels.min()) < lo or int(labels.max()) > hi):
+            raise NotImplementedError(_WIDE_LABELS)
+        return labels.to(torch.int32)
+    if _is_cai(labels):
+        if np.dtype(labels.__cuda_array_interface__["typestr"]) != np.dtype(np.int32):
+            raise TypeError("a device array of labels must be int32")
+        return labels
+    labels = np.asarray(labels)
+    if labels.dtype.kind not in "iub":
+        raise TypeError("labels must be integers")
+    if labels.dtype == np.dtype(np.int32):
+        return labels
+    if labels.dtype.itemsize >= 4 and labels.size and (int(labels.min()) < lo or int(labels.max()) > hi):
+        raise NotImplementedError(_WIDE_LABELS)
+    return labels.astype(np.int32)
+
+
+def _max_label(limg):
+    if limg.torch:
+        return int(limg.keep.max().item()) if limg.keep.numel() else 0
+    if limg.cai:
+        return None
+    return int(limg.keep.max()) if limg.keep.size else 0
+
+
+def _measures(mat, labels, num=None, top=None):
+    """One call of ``dcp_label_measures_2d``: ``(sums, boxes)`` as NumPy arrays of shape (num, 4) for the labels 1..num -- int64 pixel
+    count, sum v, sum y v, sum x v and int32 min y, max y, min x, max x.  ``mat`` None: every pixel weighs 1.  ``num`` None: the greatest
+    label; a greater ``num`` is cut down to it (the labels above are absent).  ``top``: the greatest label where the caller knows it
+    (the count :func:`label` returned) -- the plane is then not searched for it."""
+    if labels is None:
+        raise NotImplementedError("labels=None is not implemented: pass the label plane")
+    if mat is not None:
+        if _is_complex(mat):
+            raise TypeError("Complex type not supported")
+        if _is_device(mat) != _is_device(labels):
+            raise ValueError("the image and its labels must both be host arrays or both be device arrays")
+        wimg = _rows_image(mat)
+        if wimg.code not in [F.DTYPE_BY_NAME[name] for name in _MEASURED]:
+            raise NotImplementedError("measurements take bool and 8- / 16-bit integer images (their sums are exact); got %s" % (wimg.dtype,))
+    limg = _rows_image(_int32_labels(labels))
+    if mat is not None and wimg.shape != limg.shape:
+        raise ValueError("input and labels must have the same shape")
+    if top is None:
+        top = _max_label(limg)
+    if num is None:
+        if top is None:
+            raise NotImplementedError("give the labels to measure: the greatest label of a plain device array is not read back")
+        num = top
+    elif top is not None:
+        num = min(int(num), top)
+    num = max(int(num), 0)
+    height, width = limg.shape
+    if num == 0 or height == 0 or width == 0:
+        boxes = np.empty((num, 4), np.int32)
+        boxes[:] = (height, -1, width, -1)
+        return np.zeros((num, 4), np.int64), boxes
+    F.require_device()
+    sums, sptr = _new_like(limg, (num, 4), np.int64)
+    boxes, bptr = _new_like(limg, (num, 4), np.int32)
+    F.check(F.lib().dcp_label_measures_2d(wimg.ptr if mat is not None else None, limg.ptr, height, width,
+                                          _row_stride(wimg) if mat is not None else width, _row_stride(limg),
+                                          wimg.code if mat is not None else F.DTYPE_BY_NAME["uint8"], num, sptr, bptr, limg.mem, limg.device,
+                                          limg.stream))
+    return _to_host(limg, sums), _to_host(limg, boxes)
+
+
+def _index_array(index):
+    """(int64 array of the labels asked for, None for "all labels > 0")."""
+    if index is None:
+        return None
+    idx = np.asarray(index)
+    if idx.dtype.kind not in "iub" and idx.size:
+        raise TypeError("index must be an integer or a sequence of integers")
+    idx = idx.astype(np.int64)
+    if idx.size and idx.min() < 1:
+        raise NotImplementedError("index values below 1 (the background) are not measured")
+    return idx
+
+
+def _gather(sums, idx):
+    """Rows of ``sums`` for the labels ``idx`` (zeros for a label beyond the table: it has no pixels)."""
+    out = np.zeros(idx.shape + (4,), np.int64)
+    have = idx <= sums.shape[0]
+    out[have] = sums[idx[have] - 1]
+    return out
+
+
+def sum_labels(mat, labels=None, index=None):
+    """
+    Sum of the values of ``mat`` over the pixels of each label: ``scipy.ndimage.sum_labels`` (``ndi.sum``) on the GPU.
+
+    ``mat`` is a 2D bool or 8- / 16-bit integer image, ``labels`` the label plane (any integers; int32 is read in place), ``index`` a
+    label, a sequence of labels (each >= 1) or None for all pixels with a label above 0.  Returns float64 as scipy does: a scalar for
+    a scalar index, else an array of the index's shape.  The sums are accumulated in int64 on the GPU, so they are exact.
+    """
+    idx = _index_array(index)
+    sums, _ = _measures(mat, labels, None if idx is None else (int(idx.max()) if idx.size else 0))
+    if idx is None:
+        return np.float64(sums[:, 1].sum())
+    res = _gather(sums, idx)[..., 1].astype(np.float64)
+    return res[()] if res.ndim == 0 else res
+
+
+def _centroids(sums, idx):
+    """scipy's return value of center_of_mass for the labels ``idx`` (an int64 array) from the table of :func:`_measures`."""
+    rows = _gather(sums, idx).astype(np.float64)
+    norm = rows[..., 1]
+    results = [rows[..., 2] / norm, rows[..., 3] / norm]
+    if idx.ndim == 0:
+        return tuple(r[()] for r in results)
+    return [tuple(v) for v in np.array(results).T]
+
+
+def _slices(boxes, length):
+    """scipy's return value of find_objects, ``length`` entries, from the boxes of :func:`_measures`."""
+    found = [None if b[1] < 0 else (slice(int(b[0]), int(b[1]) + 1, None), slice(int(b[2]), int(b[3]) + 1, None)) for b in boxes]
+    return found + [None] * (length - len(found))
+
+
+def center_of_mass(mat, labels=None, index=None):
+    """
+    Centre of mass of the values of ``mat`` over each label: ``scipy.ndimage.center_of_mass`` on the GPU.
+
+    Arguments as for :func:`sum_labels`.  Returns a tuple ``(y, x)`` for a scalar index (or None), else a list of such tuples, as scipy
+    does; each coordinate is ``float64(sum y v) / float64(sum v)`` of exact integer sums -- scipy's own quotient bit for bit.  A label
+    without pixels (or of weight 0) divides 0 by 0: NaN and NumPy's warning, as in scipy.
+    """
+    idx = _index_array(index)
+    sums, _ = _measures(mat, labels, None if idx is None else (int(idx.max()) if idx.size else 0))
+    if idx is None:
+        tot = sums.sum(axis=0)
+        norm = np.float64(tot[1])
+        return (np.float64(tot[2]) / norm, np.float64(tot[3]) / norm)
+    return _centroids(sums, idx)
+
+
+def find_objects(labels, max_label=0):
+    """
+    Bounding boxes of the labels: ``scipy.ndimage.find_objects`` on the GPU.
+
+    Returns a list of length ``max_label`` (the greatest label if below 1): entry ``j - 1`` is ``(slice(y0, y1), slice(x0, x1))`` of
+    label ``j``, or None where no pixel carries it.
+    """
+    max_label = operator.index(max_label)
+    _, boxes = _measures(None, labels, None if max_label < 1 else max_label)
+    return _slices(boxes, max(max_label, len(boxes)))
+
+
+def check_num_dots(mat):
+    """
+    True when ``mat`` (2D binary array) holds fewer than 5 x 5 dots, too few for the parabolic fits; prints the reference's warning
+    then (reference ``preprocessing.py:251-271``).  The dots are counted by :func:`label`.
+    """
+    _, num_dots = label(mat)
+    if num_dots >= 5 * 5:
+        return False
+    print("WARNING!!! Number of detected dots: {}".format(num_dots))
+    print("is not enough for the algorithm to work!")
+    return True
+
+
+def _binary_mask(mat):
+    """uint8 mask of a 0 / 1 image of any dtype and kind; the reference's check (``preprocessing.py:991-993``) and its message, applied
+    to every value."""
+    msg = "Input not a binary image, e.i. maximum_value=1 and minimum value=0!!!"
+    if _is_torch(mat) and mat.is_cuda:
+        import torch
+        if mat.numel() == 0 or mat.max() != 1.0 or mat.min() != 0.0 or not bool(((mat == 0) | (mat == 1)).all()):
+            raise ValueError(msg)
+        return (mat != 0).to(torch.uint8)
+    if _is_cai(mat):
+        raise TypeError("takes NumPy arrays and torch tensors; label other device arrays with label()")
+    mat = np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat)
+    if np.max(mat) != 1.0 or np.min(mat) != 0.0:
+        raise ValueError(msg)
+    if not np.all((mat == 0) | (mat == 1)):
+        raise ValueError(msg)
+    return (mat != 0).astype(np.uint8)
+
+
+def get_points_dot_pattern(mat, binarize=True, ratio=0.3, thres=None):
+    """
+    The (y, x) centroids of the dots of a binary image, an (N, 2) array in label order (reference ``preprocessing.py:966-997``).
+
+    ``mat`` is a 2D image of any dtype that holds only 0 and 1 (NumPy array or torch tensor); anything else raises the reference's
+    ``ValueError``.  It is labelled and measured on the GPU as a uint8 mask, which for the values 0 and 1 is the reference's
+    arithmetic.  ``binarize`` must be False: the reference's binarization (its default, with ``ratio`` and ``thres``) rests on
+    scikit-image's Otsu threshold, ``clear_border`` and ``opening`` and raises ``NotImplementedError`` here.
+    """
+    if binarize:
+        raise NotImplementedError("binarize=True rests on scikit-image's Otsu threshold (threshold_otsu), clear_border and opening, "
+                                  "which are not implemented here: binarize the image first and pass binarize=False")
+    mask = _binary_mask(mat)
+    mat_label, num_dots = label(mask)
+    sums, _ = _measures(mask, mat_label, num_dots, top=num_dots)          # (label() has just counted them: no search for the greatest)
+    return np.asarray(_centroids(sums, np.arange(1, num_dots + 1)))
+
+
+def _host_array(mat):
+    if _is_torch(mat):
+        return mat.detach().cpu().numpy()
+    if _is_cai(mat):
+        raise TypeError("takes NumPy arrays and torch tensors")
+    return np.asarray(mat)
+
+
+def select_dots_based_size(mat, dot_size, ratio=0.3):
+    """
+    Keep the dots of a 2D binary image whose size lies within ``dot_size * (1 -/+ ratio)`` (reference ``preprocessing.py:332-360``).
+
+    Returns an int16 NumPy array (also for a tensor).  The labels and their boxes come from the GPU; as in the reference, a dot's size
+    is the sum over every pixel inside its box and a kept dot is copied box and all.
+    """
+    mat = _host_array(mat)
+    lowest = np.clip(dot_size - ratio * dot_size, 0, None)
+    highest = dot_size + ratio * dot_size
+    labels, num_dots = label(np.int16(mat))
+    _, boxes = _measures(None, labels, num_dots, top=num_dots)
+    kept = np.zeros_like(mat, dtype=np.int16)
+    for box in _slices(boxes, num_dots):
+        size = mat[box].sum()
+        if (size >= lowest) and (size <= highest):
+            kept[box] = mat[box]
+    return kept
+
+
+def select_dots_based_distance(mat, dot_dist, ratio=0.3):
+    """
+    Keep the dots one of whose three nearest neighbours lies within ``ratio`` (as a fraction of ``dot_dist``) above a whole multiple
+    of ``dot_dist`` (reference ``preprocessing.py:422-457``).
+
+    Returns an int16 NumPy array (also for a tensor).  Labels, boxes and centroids come from the GPU; the distances between the
+    centroids and the per-box copy are NumPy, in the reference's operation order.
+    """
+    mat = np.int16(_host_array(mat))
+    labels, num_dots = label(mat)
+    sums, boxes = _measures(mat, labels, num_dots, top=num_dots)          # boxes and centroids from one launch
+    boxes = _slices(boxes, num_dots)
+    cents = np.asarray(_centroids(sums, np.arange(1, num_dots + 1)))
+    kept = np.zeros_like(mat)
+    for i, box in enumerate(boxes):
+        dist = np.sort(np.sqrt((cents[i][0] - cents[:, 0]) ** 2 + (cents[i][1] - cents[:, 1]) ** 2))[1:4]
+        dist_error = (dist - (dist // dot_dist) * dot_dist) / dot_dist
+        if any(dist_error < ratio):
+            kept[box] = mat[box]
+    return kept

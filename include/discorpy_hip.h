@@ -499,6 +499,42 @@ int dcp_correlate_sym_2d(const void* src, void* dst, int height, int width, long
                          const double* weights_y, int radius_y, const double* weights_x, int radius_x,
                          int mode, double cval, int mem_kind, int device, void* stream);
 
+/* ---- dot patterns: connected components, their measurements, hole filling ----
+ * discorpy/prep/preprocessing.py:247-445 and :966-997 (scipy.ndimage.label, sum, center_of_mass, find_objects, binary_fill_holes).
+ *
+ * dcp_label_2d: dst[y, x] = the number of the connected component of src's nonzero pixels that holds (y, x), 0 where src is zero.
+ * Components are numbered 1..n in the raster order of their first pixels, as scipy.ndimage.label numbers them; `connectivity` 4 is
+ * scipy's default structure (the 3 x 3 cross), 8 the full 3 x 3 block.  A float is nonzero by its bits: NaN and denormals are, -0.0
+ * is not.
+ *   src   rows `src_row_stride` elements apart (>= width), unit column stride, any DCP_DTYPE_*
+ *   dst   dense (height, width) int32, not overlapping src;  *num_labels_out (a HOST int) receives n
+ *   mem_kind  DCP_MEM_HOST (staged up and down by the library) or DCP_MEM_DEVICE (enqueued on `stream`)
+ * THE CALL SYNCHRONISES `stream` BEFORE IT RETURNS, for device memory too: *num_labels_out is valid on return.
+ * Kernels (label_kernels.hip; dcp_debug_last_kernel() lists them): a 128 x 32 tile per workgroup labelled in LDS, the pixel pairs across
+ * tile edges united by atomic min on a parent plane, every pixel's root, the roots' ranks by a three-launch prefix sum, the relabel.  No
+ * kernel waits on another workgroup.  Scratch: 4 bytes per pixel and a count per 4096 pixels (dcp_release_scratch frees them).
+ *
+ * dcp_label_measures_2d: for every label j = 1..num_labels of `labels` (int32, rows `labels_row_stride` apart; other values are ignored)
+ *   sums[j - 1]  = { pixel count, sum v, sum y v, sum x v } over the label's pixels, int64, exact in any order of arrival
+ *   boxes[j - 1] = { min y, max y, min x, max x }, int32; { height, -1, width, -1 } for a label without pixels
+ * with v the element of `weights` at the pixel (DCP_DTYPE_BOOL, UINT8, INT8, UINT16 or INT16, rows `weights_row_stride` apart), or 1
+ * everywhere where weights is NULL (dtype is then only range-checked).  All four arrays are of one mem_kind.
+ *
+ * dcp_fill_holes_2d: dst[y, x] = 1 where src is nonzero or (y, x) lies in a component of src's ZERO pixels (4-neighbour structure) that
+ * touches no image border, else 0: scipy.ndimage.binary_fill_holes.  dst is dense (height, width) bytes.  Scratch: 8 bytes per pixel.
+ *
+ * All three: a null pointer, a height or width below 1, a stride below the width, an unknown dtype or mem_kind, a connectivity other
+ * than 4 or 8, a negative num_labels and src overlapping dst are DCP_ERR_INVALID_ARG; height * width above 2^31 - 1 (labels and pixel
+ * indices are int32), weights of another type and height * width * max(height, width) * 65536 >= 2^63 (an int64 sum could overflow)
+ * are DCP_ERR_UNSUPPORTED; all before any device call. */
+int dcp_label_2d(const void* src, int32_t* dst, int height, int width, long src_row_stride, int dtype, int connectivity,
+                 int* num_labels_out, int mem_kind, int device, void* stream);
+int dcp_label_measures_2d(const void* weights, const int32_t* labels, int height, int width, long weights_row_stride,
+                          long labels_row_stride, int dtype, int num_labels, int64_t* sums, int32_t* boxes, int mem_kind, int device,
+                          void* stream);
+int dcp_fill_holes_2d(const void* src, uint8_t* dst, int height, int width, long src_row_stride, int dtype, int mem_kind, int device,
+                      void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the

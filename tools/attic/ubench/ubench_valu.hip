@@ -1,6 +1,6 @@
 // ubench_valu.hip -- issue cost of single gfx950 VALU / LDS instructions, relative to v_fma_f32 (2 cycles per wave64 on a SIMD-32,
 // MI355X_MICROARCH.md): every SIMD runs 8 waves that issue long runs of ONE instruction on four independent register sets.
-//   hipcc --offload-arch=gfx950 -O2 tools/ubench_valu.hip -o tools/ubench_valu && tools/ubench_valu
+//   hipcc --offload-arch=gfx950 -O2 tools/attic/ubench/ubench_valu.hip -o tools/attic/ubench/ubench_valu && tools/attic/ubench/ubench_valu
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>

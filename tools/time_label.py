@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Time connected-component labelling (dcp_label_2d), labelling plus the dot measurements (dcp_label_measures_2d) and hole filling
+(dcp_fill_holes_2d) on device-resident images: the default route (x_label_lds = 1: a 128 x 32 tile per workgroup labelled in LDS, then
+the tile seams) against the global union over every pixel pair (x_label_lds = 0), alternated in one process, and scipy.ndimage on the
+same box.  Images of 2048^2 and 4096^2: a grid of dots of radius 8 on a pitch of 40 in uint8 and float32, and one image of random noise
+of density 0.55 in uint8 (large ragged components: the hard case for a union-find).
+
+Per case: warm-up calls of both routes, then `--rounds` (at least five) rounds; a round times `--reps` back-to-back calls of the tiled
+route with a host clock around calls that end in a stream synchronise (dcp_label_2d synchronises by itself), then the same of the global
+route.  Printed in ms per call: the median round of each route, the global route's round-to-round spread (max - min), the difference
+tiled - global and whether it is within that spread (the bar for keeping x_label_lds = 1 the default: it is not slower than the global
+route by more than that route's own spread, on the dot grid and on the noise), whether the two outputs are equal, and the number of
+labels.  scipy is timed at the `--scipy-side` (2048) only, once per case, and there the line also carries the ratio scipy / GPU and
+whether scipy's output equals the GPU's.  The last line is the core clock and package power under the 4096^2 uint8 label call.
+
+    python tools/time_label.py [--sides 2048,4096] [--dtypes uint8,float32] [--rounds 5] [--reps 3] [--no-scipy]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def dot_grid(side, radius=8, pitch=40):
+    y, x = np.mgrid[0:side, 0:side]
+    return ((y % pitch - pitch // 2) ** 2 + (x % pitch - pitch // 2) ** 2 <= radius * radius)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sides", default="2048,4096")
+    ap.add_argument("--dtypes", default="uint8,float32")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--scipy-side", type=int, default=2048, help="the side at which scipy is timed and compared (0 or --no-scipy: never)")
+    ap.add_argument("--no-scipy", action="store_true")
+    a = ap.parse_args()
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    import bench
+    from discorpy_amd import _ffi as F
+    L = F.lib()
+    F.require_device()
+    dev = -1
+    clock_call = None
+    for side in [int(s) for s in a.sides.split(",")]:
+        images = [("dots", np.dtype(name), dot_grid(side).astype(name)) for name in a.dtypes.split(",")]
+        images.append(("noise", np.dtype(np.uint8), (np.random.default_rng(55).random((side, side)) < 0.55).astype(np.uint8)))
+        for what, dt, img in images:
+            code = F.DTYPE_BY_NAME[dt.name]
+            src = F.DeviceBuffer(img.nbytes, dev).upload(img)
+            lab = {v: F.DeviceBuffer(img.size * 4, dev) for v in (1, 0)}
+            filled = {v: F.DeviceBuffer(img.size, dev) for v in (1, 0)}
+            num = F.C.c_int(0)
+            F.check(L.dcp_label_2d(src.ptr, lab[1].ptr, side, side, side, code, 4, F.C.byref(num), F.MEM_DEVICE, dev, None))
+            count = max(num.value, 1)
+            sums, boxes = F.DeviceBuffer(count * 32, dev), F.DeviceBuffer(count * 16, dev)
+
+            def label(v):
+                F.check(L.dcp_label_2d(src.ptr, lab[v].ptr, side, side, side, code, 4, F.C.byref(num), F.MEM_DEVICE, dev, None))
+
+            def label_measure(v):
+                label(v)
+                F.check(L.dcp_label_measures_2d(src.ptr if dt.itemsize <= 2 else None, lab[v].ptr, side, side, side, side, code, num.value, sums.ptr,
+                                                boxes.ptr, F.MEM_DEVICE, dev, None))
+                F.check(L.dcp_stream_synchronize(dev, None))
+
+            def fill(v):
+                F.check(L.dcp_fill_holes_2d(src.ptr, filled[v].ptr, side, side, side, code, F.MEM_DEVICE, dev, None))
+                F.check(L.dcp_stream_synchronize(dev, None))
+
+            for op_name, op in (("label", label), ("label + measures", label_measure), ("fill_holes", fill)):
+                def timed(v):
+                    F.set_option("x_label_lds", v)
+                    t0 = time.perf_counter()
+                    for _r in range(a.reps):
+                        op(v)
+                    return (time.perf_counter() - t0) * 1e3 / a.reps
+                for v in (1, 0):
+                    F.set_option("x_label_lds", v)
+                    for _ in range(a.warmup):
+                        op(v)
+                rounds = {1: [], 0: []}
+                for _ in range(a.rounds):
+                    for v in (1, 0):
+                        rounds[v].append(timed(v))
+                F.set_option("x_label_lds", 1)
+                tiled, glob = float(np.median(rounds[1])), float(np.median(rounds[0]))
+                spread = max(rounds[0]) - min(rounds[0])
+                if op is fill:
+                    out1, out0 = filled[1].download(img.shape, np.bool_), filled[0].download(img.shape, np.bool_)
+                else:
+                    out1, out0 = lab[1].download(img.shape, np.int32), lab[0].download(img.shape, np.int32)
+                line = ("%-5s %-8s %4d x %-4d %-16s tiled %9.4f ms (rounds %.4f .. %.4f)  global %9.4f ms (rounds %.4f .. %.4f, spread %.4f)"
+                        "  tiled - global %+.4f ms: %s  routes equal: %s  labels: %d" % (
+                            what, dt.name, side, side, op_name, tiled, min(rounds[1]), max(rounds[1]), glob, min(rounds[0]), max(rounds[0]), spread,
+                            tiled - glob, "within the bar" if tiled - glob <= spread else "MISSES the bar", np.array_equal(out1, out0), num.value))
+                if not a.no_scipy and side == a.scipy_side:
+                    from scipy import ndimage as ndi
+                    t0 = time.perf_counter()
+                    if op is fill:
+                        ref = ndi.binary_fill_holes(img)
+                    else:
+                        ref, ref_num = ndi.label(img)
+                        if op is label_measure:
+                            idx = np.arange(1, ref_num + 1)
+                            weights = img if dt.itemsize <= 2 else ref > 0
+                            ndi.sum_labels(weights, ref, idx), ndi.center_of_mass(weights, ref, idx), ndi.find_objects(ref)
+                    cpu_ms = (time.perf_counter() - t0) * 1e3
+                    line += "  scipy %9.1f ms  ratio %8.1f  equal to scipy: %s" % (cpu_ms, cpu_ms / tiled, np.array_equal(out1, ref))
+                print(line, flush=True)
+            if side >= 4096 and what == "dots" and dt == np.uint8:
+                clock_call = (src, lab[1], side, code)
+            for buf in [sums, boxes, filled[1], filled[0], lab[0]] + ([] if clock_call and clock_call[0] is src else [src, lab[1]]):
+                buf.free()
+    if clock_call:
+        src, out, side, code = clock_call
+        num = F.C.c_int(0)
+        clk = bench.clocks_under_load(lambda: F.check(L.dcp_label_2d(src.ptr, out.ptr, side, side, side, code, 4, F.C.byref(num), F.MEM_DEVICE, dev, None)),
+                                      lambda: F.check(L.dcp_stream_synchronize(dev, None)))
+        print("clock under the %d x %d uint8 label call: %s" % (side, side, clk), flush=True)
+
+
+if __name__ == "__main__":
+    main()
