@@ -118,6 +118,12 @@ SIGNATURES = {
     "dcp_label_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, C.POINTER(_int), _int, _int, _vp]),
     "dcp_label_measures_2d": (_int, [_vp, _vp, _int, _int, C.c_long, C.c_long, _int, _int, _vp, _vp, _int, _int, _vp]),
     "dcp_fill_holes_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
+    "dcp_abs_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
+    "dcp_minmax_2d": (_int, [_vp, _int, _int, C.c_long, _int, _dp, C.POINTER(_i64), _int, _int, _vp]),
+    "dcp_histogram_2d": (_int, [_vp, _int, _int, C.c_long, _int, _vp, _int, _i64, _vp, _int, _int, _vp]),
+    "dcp_threshold_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _dbl, _vp, _int, _int, _vp]),
+    "dcp_clear_border_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _int, _vp]),
+    "dcp_morph_cross_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
     "dcp_debug_counters": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_bounds": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_last_kernel": (C.c_char_p, []),

@@ -24,7 +24,7 @@ const char* last_error();
     }                                                                                                      \
   } while (0)
 
-extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync, g_spline_frames, g_median_lds, g_gauss_lds, g_label_lds;
+extern std::atomic<int> g_tile_rows, g_xcd_remap, g_coef_lds, g_d_chunk, g_pipe_depth, g_lds_gather, g_stack_chunk_kb, g_stack_lds, g_host_duplex, g_host_bands, g_tile_cert, g_wg_box, g_wg_per_cu, g_stack_wg, g_int_exact, g_host_direct, g_tall_tiles, g_store_wait, g_fused_wg, g_any_order, g_host_band_sync, g_spline_frames, g_median_lds, g_gauss_lds, g_label_lds, g_hist_lds, g_morph_fused;
 dcp::LaunchOpts current_opts();
 
 // Selects `device` for the calling thread for the lifetime of the object (no-op for device < 0).
@@ -226,6 +226,12 @@ int host_round_trip(const HostTrip& t, hipStream_t st, Launch&& launch) {
   DCP_HIP(hipStreamSynchronize(st));
   return DCP_OK;
 }
+
+// api_label.cpp: the checks the plane entry points share (labelling, hole filling, binarization), before any device call; dst_elem = 0:
+// the call has no destination plane.  *host = DCP_MEM_HOST
+int check_plane_call(const void* src, const void* dst, int height, int width, long src_row_stride, int dtype, size_t dst_elem, int mem_kind, bool* host);
+// api_label.cpp: the round trip of such a call -- the rows packed on the way up, height * width * dst_elem bytes back (none without dst)
+HostTrip packed_rows(const void* src, void* dst, int height, int width, long src_row_stride, size_t esz, size_t dst_elem);
 
 // api_spline.cpp: the spline executor (c.exec == kExecSpline; the device is selected)
 int run_spline(const FrameCall& c);

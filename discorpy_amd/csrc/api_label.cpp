@@ -1,21 +1,22 @@
-// api_label.cpp -- dcp_label_2d, dcp_label_measures_2d and dcp_fill_holes_2d of the C ABI (include/discorpy_hip.h): the argument checks, the
-// working planes (leased from the spline workspace), the staged round trip of host memory and the launches of label_kernels.hip.
+// api_label.cpp -- dcp_label_2d, dcp_label_measures_2d, dcp_fill_holes_2d and dcp_clear_border_2d of the C ABI (include/discorpy_hip.h): the
+// argument checks (shared with api_binarize.cpp), the working planes (leased from the spline workspace), the staged round trip of host
+// memory and the launches of label_kernels.hip.
 #include "api_common.h"
 
 using namespace dcpapi;
 
-namespace {
+namespace dcpapi {
 
-// the checks the image entry points share; *host = DCP_MEM_HOST
-int check_plane_call(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, size_t dst_elem, int mem_kind, bool* host) {
+int check_plane_call(const void* src, const void* dst, int height, int width, long src_row_stride, int dtype, size_t dst_elem, int mem_kind, bool* host) {
   int rc;
   if ((rc = mem_kind_of(mem_kind, host)) != DCP_OK) return rc;
   if (dtype < 0 || dtype >= dcp::kNumElemTypes) return fail(DCP_ERR_INVALID_ARG, "unknown dtype %d", dtype);
-  if (!src || !dst) return fail(DCP_ERR_INVALID_ARG, "null src / dst pointer");
+  if (!src || (dst_elem && !dst)) return fail(DCP_ERR_INVALID_ARG, "null src / dst pointer");
   if (height < 1 || width < 1) return fail(DCP_ERR_INVALID_ARG, "height and width must be at least 1 (got %d x %d)", height, width);
   if (src_row_stride < width) return fail(DCP_ERR_INVALID_ARG, "src_row_stride %ld is below the width %d", src_row_stride, width);
   if ((int64_t)height * (int64_t)width > 2147483647LL)
     return fail(DCP_ERR_UNSUPPORTED, "height * width = %lld: labels and pixel indices are int32, at most 2^31 - 1 pixels", (long long)height * width);
+  if (!dst_elem) return DCP_OK;
   const size_t esz = (size_t)dcp::elem_size(dtype);
   const char *s0 = (const char*)src, *s1 = s0 + ((size_t)(height - 1) * (size_t)src_row_stride + (size_t)width) * esz;
   const char *d0 = (const char*)dst, *d1 = d0 + (size_t)height * (size_t)width * dst_elem;
@@ -34,7 +35,7 @@ HostTrip packed_rows(const void* src, void* dst, int height, int width, long src
   return t;
 }
 
-}  // namespace
+}  // namespace dcpapi
 
 extern "C" {
 
@@ -92,6 +93,32 @@ int dcp_fill_holes_2d(const void* src, uint8_t* dst, int height, int width, long
   return host_round_trip(packed_rows(src, dst, height, width, src_row_stride, (size_t)dcp::elem_size(dtype), sizeof(uint8_t)), st,
                          [&](const void* dsrc, void* ddst, void*, void*) {
                            return dcp::launch_fill_holes(dsrc, static_cast<uint8_t*>(ddst), parent, root, height, width, (int64_t)width, dtype, use_lds, st);
+                         });
+}
+
+int dcp_clear_border_2d(const void* src, uint8_t* dst, int height, int width, long src_row_stride, int dtype, int connectivity, int invert,
+                        int mem_kind, int device, void* stream) {
+  bool host = false;
+  int rc;
+  if ((rc = check_plane_call(src, dst, height, width, src_row_stride, dtype, sizeof(uint8_t), mem_kind, &host)) != DCP_OK) return rc;
+  if (connectivity != 4 && connectivity != 8) return fail(DCP_ERR_INVALID_ARG, "connectivity must be 4 or 8 (got %d)", connectivity);
+  if (invert != 0 && invert != 1) return fail(DCP_ERR_INVALID_ARG, "invert must be 0 or 1 (got %d)", invert);
+  DeviceScope scope(device);
+  if (scope.status != hipSuccess) return fail(DCP_ERR_HIP, "cannot select device %d: %s", device, hipGetErrorString(scope.status));
+  const bool use_lds = g_label_lds.load() != 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)height * (size_t)width;
+  WorkspaceLease lease;          // the parent plane of the components and the plane of their roots
+  if ((rc = lease.acquire(2 * n * sizeof(int32_t), st)) != DCP_OK) return rc;
+  int32_t *parent = static_cast<int32_t*>(lease.buf), *root = parent + n;
+  if (!host) {
+    DCP_HIP(dcp::launch_clear_border(src, dst, parent, root, height, width, (int64_t)src_row_stride, dtype, connectivity == 8, invert != 0, use_lds, st));
+    return DCP_OK;
+  }
+  return host_round_trip(packed_rows(src, dst, height, width, src_row_stride, (size_t)dcp::elem_size(dtype), sizeof(uint8_t)), st,
+                         [&](const void* dsrc, void* ddst, void*, void*) {
+                           return dcp::launch_clear_border(dsrc, static_cast<uint8_t*>(ddst), parent, root, height, width, (int64_t)width, dtype,
+                                                           connectivity == 8, invert != 0, use_lds, st);
                          });
 }
 

@@ -296,6 +296,34 @@ hipError_t launch_label(const void* src, int32_t* dst, int32_t* parent, int32_t*
 // scipy.ndimage.binary_fill_holes into dst (dense H x W bytes of 0 / 1); `parent` and `root`: H W int32 of device scratch each
 hipError_t launch_fill_holes(const void* src, uint8_t* dst, int32_t* parent, int32_t* root, int H, int W, int64_t src_stride, int dtype,
                              bool use_lds, hipStream_t stream);
+// skimage.segmentation.clear_border on a binary image into dst (dense H x W bytes of 0 / 1): the set pixels (invert: the ZERO pixels)
+// whose component (conn8: full 3 x 3 structure, else the cross) has no pixel on the image border.  Scratch as for launch_fill_holes
+hipError_t launch_clear_border(const void* src, uint8_t* dst, int32_t* parent, int32_t* root, int H, int W, int64_t src_stride, int dtype,
+                               bool conn8, bool invert, bool use_lds, hipStream_t stream);
+// binarize_kernels.hip: the steps of discorpy.prep.preprocessing.binarization that labelling does not cover.  Rows of src `src_stride`
+// elements apart, every dst dense.
+constexpr int kHistLdsMaxBins = 4096;          // up to this many bins a workgroup counts in LDS (32-bit, flushed with 64-bit atomics);
+                                               // above it (a 16-bit bincount has up to 65536) every element adds to global memory
+constexpr int kMorphTW = 128, kMorphTH = 32;   // morph_cross_kernel's output tile; its LDS planes carry a halo of 1 (one op) or 2 (opening)
+constexpr int kReduceMaxBlocks = 1024;         // workgroups of minmax_kernel / histogram_kernel (they stride over the rows)
+// np.abs: floats lose their sign bit, signed integers wrap at their minimum, unsigned / bool are copied.  Any ElemType
+hipError_t launch_abs(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, hipStream_t stream);
+// out[0] = minimum, out[1] = maximum as NumPy's a.min() / a.max() give them (NaN if any element is), nonfinite[0] = elements that are NaN
+// or infinite; kF32, kF64 and the 8- / 16-bit integers.  `partials`: 3 * kReduceMaxBlocks doubles of device scratch
+hipError_t launch_minmax(const void* src, int H, int W, int64_t src_stride, int dtype, double* partials, double* out, long long* nonfinite,
+                         hipStream_t stream);
+// counts[nbins] (int64, zeroed here).  edges != null (device memory, nbins + 1 ascending values of the plane's float type): bin i holds
+// edges[i] <= a < edges[i + 1], the last one a == edges[nbins] too, anything else (NaN included) is not counted.  edges == null (8- / 16-bit
+// integers): bin a - first, elements outside [first, first + nbins) are not counted.  use_lds = false: global atomics at any bin count
+hipError_t launch_histogram(const void* src, int H, int W, int64_t src_stride, int dtype, const void* edges, int nbins, long long first,
+                            long long* counts, bool use_lds, hipStream_t stream);
+// dst = (double)a > thres (NaN: 0) as bytes; *count (device int64, may be null) += the number of set pixels.  Any ElemType
+hipError_t launch_threshold(const void* src, uint8_t* dst, int H, int W, int64_t src_stride, int dtype, double thres, long long* count,
+                            hipStream_t stream);
+// grey erosion (op 0), dilation (op 1) or opening (op 2) of a uint8 plane by the 3 x 3 cross over the in-image neighbours only.  Opening:
+// one launch (both steps on a tile with a halo of 2 in LDS) when fused, else erosion into `tmp` (H W bytes of device scratch) and dilation
+hipError_t launch_morph_cross(const uint8_t* src, uint8_t* dst, uint8_t* tmp, int H, int W, int64_t src_stride, int op, bool fused,
+                              hipStream_t stream);
 // per label 1..num of `labels` (rows l_stride apart; other values are ignored): sums[num][4] = pixel count, sum v, sum y v, sum x v over
 // its pixels and boxes[num][4] = min y, max y, min x, max x ((H, -1, W, -1) for an absent label); v from `weights` (kBool, kU8, kI8, kU16
 // or kI16; rows w_stride apart) or 1 everywhere where weights is null

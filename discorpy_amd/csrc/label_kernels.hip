@@ -29,6 +29,10 @@
 // border pixel's root (all stores write the same value; it is read in the next launch only), fill_holes_kernel writes
 // dst = foreground || parent[root] != -2.
 //
+// Border components (skimage.segmentation.clear_border of a binary image, dcp_clear_border_2d): the same with the predicate and the
+// connectivity turned round -- the first three stages on the SET pixels (or, `invert`, the zero ones) at connectivity 8 or 4,
+// label_border_kernel, then clear_border_kernel writes dst = foreground && parent[root] != -2.
+//
 // Measurements: label_measure_kernel, a wave per 64 pixels of a row.  Lanes of one run of equal labels combine by a segmented
 // shuffle scan (count, sum v, sum lane v; y is the wave's), the run's last lane adds to the label's four int64 sums and to its box
 // with 32-bit min / max.  Integer atomics: the result does not depend on arrival order.
@@ -377,6 +381,16 @@ __global__ void __launch_bounds__(kLabelBlock) fill_holes_kernel(const int32_t* 
   dst[i] = (r < 0 || parent[r] != kLabelFlagged) ? 1 : 0;
 }
 
+// clear_border: the foreground's own components; a pixel stays where its root's slot was not flagged by label_border_kernel
+__global__ void __launch_bounds__(kLabelBlock) clear_border_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ parent,
+                                                                   uint8_t* __restrict__ dst, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kLabelBlock + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = root[i];          // -1 where the pixel is background
+  if (r >= 0) LABEL_AT(r, n, 43);
+  dst[i] = (r >= 0 && parent[r] != kLabelFlagged) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ measurements
 
 enum WeightKind : int { kWNone = 0, kWU8, kWI8, kWU16, kWI16 };
@@ -562,6 +576,21 @@ hipError_t launch_fill_holes(const void* src, uint8_t* dst, int32_t* parent, int
   hipLaunchKernelGGL(fill_holes_kernel, dim3(blocks_of(n)), dim3(kLabelBlock), 0, stream, root, parent, dst, n);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   snprintf(name, sizeof(name), "%s + label_border_kernel + fill_holes_kernel", desc);
+  set_last_kernel_name(name);
+  return hipSuccess;
+}
+
+hipError_t launch_clear_border(const void* src, uint8_t* dst, int32_t* parent, int32_t* root, int H, int W, int64_t src_stride, int dtype,
+                               bool conn8, bool invert, bool use_lds, hipStream_t stream) {
+  char desc[192], name[256];
+  hipError_t e = launch_label_roots(src, parent, root, H, W, src_stride, dtype, conn8, invert, use_lds, stream, desc, sizeof(desc));
+  if (e != hipSuccess) return e;
+  const int64_t n = (int64_t)H * W;
+  hipLaunchKernelGGL(label_border_kernel, dim3(blocks_of(2 * ((int64_t)W + H))), dim3(kLabelBlock), 0, stream, root, parent, H, W);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(clear_border_kernel, dim3(blocks_of(n)), dim3(kLabelBlock), 0, stream, root, parent, dst, n);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  snprintf(name, sizeof(name), "%s + label_border_kernel + clear_border_kernel", desc);
   set_last_kernel_name(name);
   return hipSuccess;
 }

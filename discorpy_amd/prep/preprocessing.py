@@ -9,8 +9,14 @@
 * :func:`check_num_dots`, :func:`get_points_dot_pattern` (``binarize=False``), :func:`select_dots_based_size`,
   :func:`select_dots_based_distance`   the reference's functions on top of them: same names, arguments, messages and prints
 
-The rest of the reference's module (Otsu threshold, ``clear_border``, morphology and ``regionprops``, the Radon-based angle search)
-rests on scikit-image and is out of scope here: there is nothing to compare an implementation against.
+* :func:`threshold_otsu`, :func:`clear_border`, :func:`opening`, :func:`binarization`   the reference's ``binarization``
+  (``preprocessing.py:216-248``) and the three scikit-image functions it calls, each restated through what NumPy and scipy define:
+  ``np.histogram`` / ``np.bincount`` and the published Otsu formula, ``scipy.ndimage.label`` with the full 3 x 3 structure,
+  ``scipy.ndimage.grey_opening`` with the 3 x 3 cross.  Results equal those composites element for element; scikit-image itself is
+  not installed where this was written, so the link to it is by construction and UNVERIFIED ("Binarization")
+
+The rest of the reference's module (``regionprops`` behind ``select_dots_based_ratio``, the Radon-based angle search) rests on
+scikit-image and is out of scope here: there is nothing to compare an implementation against.
 
 The median runs as a hand-written HIP kernel through ``dcp_median_filter_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/median_kernels.hip``): it SELECTS the element of rank ``(size_y * size_x) // 2`` of every window by a binary search on
@@ -25,6 +31,15 @@ components in the raster order of their first pixels -- scipy's numbering, witho
 formed in NumPy float64 as scipy forms them, so for bool and 8- / 16-bit integer images (every partial sum an integer below 2**53)
 they equal scipy's bit for bit.  Float and wider integer weights raise ``NotImplementedError``: the reference only ever measures
 binary images.  :func:`binary_fill_holes` is the same labelling run on the complement (4-neighbour structure) plus a border flag.
+
+Binarization (``csrc/binarize_kernels.hip``; ``dcp_clear_border_2d`` beside the labelling it reuses): the GPU delivers exact integers --
+minimum and maximum, int64 bin counts, the number of set pixels, 0 / 1 planes -- and the few quotients of the Otsu formula are formed
+in NumPy float64 on at most 65536 numbers, the division of labour of the centroids.  :func:`binarization` uploads a NumPy image once,
+runs every step on device planes and downloads the int16 result once; a tensor stays on torch's current stream.  Departures from the
+reference: the contrast is inverted iff ``2 * count > height * width`` on the exact count of set pixels (the reference's float32
+``np.sum`` is exact below 2**24 set pixels and may round above); a given ``thres`` reaches the kernel as one double (NumPy 2's
+promotion: a Python float against a float32 image is rounded to float32, a NumPy float64 scalar promotes the comparison to float64), so
+64-bit integer images beyond 2**53 are compared after rounding to double, as NumPy compares them with a float threshold.
 
 Where the median differs from scipy:
 
@@ -50,6 +65,8 @@ from ..post.postprocessing import _Image, _is_cai, _is_torch
 
 __all__ = ["normalization", "median_filter"]
 # the dot-pattern route (labelling, measurements, hole filling and the reference's functions on top of them)
+# the binarization of a dot image in front of that route
+BINARIZATION = ["threshold_otsu", "clear_border", "opening", "binarization"]
 DOT_PATTERN = ["label", "sum_labels", "center_of_mass", "find_objects", "binary_fill_holes", "check_num_dots", "get_points_dot_pattern",
                "select_dots_based_size", "select_dots_based_distance"]
 
@@ -473,8 +490,8 @@ def get_points_dot_pattern(mat, binarize=True, ratio=0.3, thres=None):
 
     ``mat`` is a 2D image of any dtype that holds only 0 and 1 (NumPy array or torch tensor); anything else raises the reference's
     ``ValueError``.  It is labelled and measured on the GPU as a uint8 mask, which for the values 0 and 1 is the reference's
-    arithmetic.  ``binarize`` must be False: the reference's binarization (its default, with ``ratio`` and ``thres``) rests on
-    scikit-image's Otsu threshold, ``clear_border`` and ``opening`` and raises ``NotImplementedError`` here.
+    arithmetic.  ``binarize`` must be False: the reference's default (with ``ratio`` and ``thres``) raises ``NotImplementedError``
+    here.  Binarize first -- ``get_points_dot_pattern(binarization(mat, ratio, thres), binarize=False)`` -- with :func:`binarization`.
     """
     if binarize:
         raise NotImplementedError("binarize=True rests on scikit-image's Otsu threshold (threshold_otsu), clear_border and opening, "
@@ -533,3 +550,371 @@ def select_dots_based_distance(mat, dot_dist, ratio=0.3):
         if any(dist_error < ratio):
             kept[box] = mat[box]
     return kept
+
+
+# --------------------------------------------------------------------------- binarization
+
+_HISTOGRAMMED = ("float32", "float64", "uint8", "int8", "uint16", "int16")
+
+
+class _PlaneView:
+    """A 2-D window of a device array (anything with ``__cuda_array_interface__``): ``view[y0:y1, x0:x1]`` is another window of the
+    same allocation, read in place through its row stride."""
+
+    def __init__(self, base):
+        cai = base.__cuda_array_interface__
+        self.base = getattr(base, "base", base)          # keeps the allocation alive
+        self.dtype = np.dtype(cai["typestr"])
+        self.shape = tuple(int(v) for v in cai["shape"])
+        if len(self.shape) != 2:
+            raise ValueError("expected a 2-D array")
+        st = cai.get("strides")
+        self.strides = tuple(int(v) for v in st) if st is not None else (self.shape[1] * self.dtype.itemsize, self.dtype.itemsize)
+        self.ptr = int(cai["data"][0])
+        self.stream = cai.get("stream")
+
+    @property
+    def __cuda_array_interface__(self):
+        cai = {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "version": 3, "strides": self.strides}
+        if self.stream is not None:
+            cai["stream"] = self.stream
+        return cai
+
+    def __getitem__(self, key):
+        if not (isinstance(key, tuple) and len(key) == 2 and all(isinstance(k, slice) for k in key)):
+            raise IndexError("a device plane takes two slices")
+        view = _PlaneView(self)
+        for axis, k in enumerate(key):
+            start, stop, step = k.indices(self.shape[axis])
+            if step != 1:
+                raise IndexError("a device plane takes slices of step 1")
+            view.ptr += start * self.strides[axis]
+            view.shape = view.shape[:axis] + (max(stop - start, 0),) + view.shape[axis + 1:]
+        return view
+
+
+def _real_plane(mat):
+    """``mat`` as a 2-D :class:`_Image` of a real element type (the module's ``TypeError`` for complex input)."""
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    return _rows_image(mat)
+
+
+def _abs_plane(img):
+    """``np.abs`` of the plane of ``img`` (an :class:`_Image`) as a fresh array of its kind; unsigned and bool planes come back as they are."""
+    if np.dtype(_np_name(img)).kind in "ub":
+        return img.keep
+    height, width = img.shape
+    res, rptr = _new_like(img, (height, width), _np_name(img))
+    F.check(F.lib().dcp_abs_2d(img.ptr, rptr, height, width, _row_stride(img), img.code, img.mem, img.device, img.stream))
+    return res
+
+
+def _np_name(img):
+    """NumPy name of the element type of an :class:`_Image`."""
+    return str(img.dtype).replace("torch.", "") if img.torch else np.dtype(img.dtype).name
+
+
+def _minmax(img):
+    """(minimum, maximum, number of non-finite elements) of the plane of ``img``; the first two as Python floats holding the element
+    exactly (NaN where any element is NaN, as ``a.min()`` gives it).  Waits for the image's stream."""
+    out = (ctypes.c_double * 2)()
+    bad = ctypes.c_int64(0)
+    height, width = img.shape
+    F.check(F.lib().dcp_minmax_2d(img.ptr, height, width, _row_stride(img), img.code, out, ctypes.byref(bad), img.mem, img.device, img.stream))
+    return out[0], out[1], int(bad.value)
+
+
+def _histogram(img, nbins, edges=None, first=0):
+    """int64 counts of the plane of ``img``: between the ``nbins + 1`` ``edges`` (a NumPy array of the plane's float type; the last bin
+    closed) or, for 8- / 16-bit integers, per value from ``first``.  Waits for the image's stream."""
+    counts = np.empty(nbins, np.int64)
+    height, width = img.shape
+    if edges is not None:
+        edges = np.ascontiguousarray(edges, dtype=_np_name(img))
+        assert edges.shape == (nbins + 1,)
+    F.check(F.lib().dcp_histogram_2d(img.ptr, height, width, _row_stride(img), img.code, None if edges is None else edges.ctypes.data, nbins,
+                                     int(first), counts.ctypes.data, img.mem, img.device, img.stream))
+    return counts
+
+
+def _threshold_plane(img, thres):
+    """(uint8 plane of ``(double)a > thres`` of the kind of ``img``, the exact number of set pixels).  Waits for the image's stream."""
+    height, width = img.shape
+    mask, mptr = _new_like(img, (height, width), np.uint8)
+    if img.mem == F.MEM_HOST:
+        count = ctypes.c_int64(0)
+        F.check(F.lib().dcp_threshold_2d(img.ptr, mptr, height, width, _row_stride(img), img.code, float(thres), ctypes.addressof(count), img.mem,
+                                         img.device, img.stream))
+        return mask, int(count.value)
+    if img.torch:
+        import torch
+        count = torch.zeros(1, dtype=torch.int64, device=img.keep.device)
+        cptr = count.data_ptr()
+    else:
+        count = F.DeviceArray((1,), np.int64, img.device).copy_from_host(np.zeros(1, np.int64))
+        cptr = count.ptr
+    F.check(F.lib().dcp_threshold_2d(img.ptr, mptr, height, width, _row_stride(img), img.code, float(thres), cptr, img.mem, img.device, img.stream))
+    return mask, int(_to_host(img, count)[0])
+
+
+def _clear_border_plane(img, invert=False, conn=8):
+    """uint8 plane of the kind of ``img``: its nonzero (``invert``: zero) pixels whose component (``conn`` 4 or 8) touches no border."""
+    height, width = img.shape
+    res, rptr = _new_like(img, (height, width), np.uint8)
+    F.check(F.lib().dcp_clear_border_2d(img.ptr, rptr, height, width, _row_stride(img), img.code, conn, 1 if invert else 0, img.mem, img.device,
+                                        img.stream))
+    return res
+
+
+def _morph_plane(img, op):
+    """Erosion (0), dilation (1) or opening (2) by the 3 x 3 cross of the uint8 / bool plane of ``img``, as a uint8 plane of its kind."""
+    height, width = img.shape
+    res, rptr = _new_like(img, (height, width), np.uint8)
+    F.check(F.lib().dcp_morph_cross_2d(img.ptr, rptr, height, width, _row_stride(img), op, img.mem, img.device, img.stream))
+    return res
+
+
+def _as_kind(mat):
+    """(``mat`` as the array the steps work on, "torch" / "numpy"): a ROCm tensor stays, anything else becomes a NumPy array."""
+    if _is_torch(mat) and mat.is_cuda:
+        return mat, "torch"
+    if _is_cai(mat):
+        raise TypeError("takes NumPy arrays and torch tensors")
+    return np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat), "numpy"
+
+
+def _select_roi(mat, ratio, square=False):
+    """
+    The region of interest around the middle of an image (reference ``preprocessing.py:161-191``): a view, never a copy.
+
+    ``mat`` is a 2D array, tensor or device plane, ``ratio`` the ROI's size over the image's (clipped to [0.05, 1]); ``square``
+    selects a square of that ratio of the shorter side.
+    """
+    (height, width) = mat.shape
+    ratio = np.clip(ratio, 0.05, 1.0)
+    if square is True:
+        c_hei = height // 2
+        c_wid = width // 2
+        radi = int(ratio * min(height, width)) // 2
+        return mat[c_hei - radi:c_hei + radi, c_wid - radi:c_wid + radi]
+    depad_hei = int((height - ratio * height) / 2)
+    depad_wid = int((width - ratio * width) / 2)
+    return mat[depad_hei:height - depad_hei, depad_wid:width - depad_wid]
+
+
+def _invert_dots_contrast(mat):
+    """
+    Invert a 2D binary array (NumPy array or torch tensor) where more than half of it is set, so that dots are white (reference
+    ``preprocessing.py:194-213``).  The set pixels are counted on the GPU and the test is ``2 * count > height * width`` in integers;
+    the reference's float32 ``np.sum`` is exact below 2**24 set pixels and may round above.
+    """
+    mat, _ = _as_kind(mat)
+    (height, width) = mat.shape
+    if height == 0 or width == 0:
+        return mat
+    F.require_device()
+    _, count = _threshold_plane(_real_plane(mat), 0.0)
+    if 2 * count > height * width:
+        mat = mat.max() - mat
+    return mat
+
+
+def threshold_otsu(image, nbins=256):
+    """
+    Otsu's threshold of a 2D image: scikit-image's ``threshold_otsu(image, nbins)`` restated through NumPy.
+
+    Parameters
+    ----------
+    image : array_like
+        2D array (NumPy array, ROCm torch tensor or device array) of float32 / float64 or an 8- / 16-bit integer type; a strided
+        view (a region of interest) is read in place.
+    nbins : int
+        Number of bins of a float image's histogram (integer images are counted per value).
+
+    Returns
+    -------
+    NumPy scalar
+        The centre of the bin that maximises the between-class variance: for floats a centre of ``np.histogram(image, nbins)``, of
+        the image's type; for integers a value of ``arange(min, max + 1)``.  A constant image returns its value.  Minimum, maximum
+        and the int64 counts come from the GPU; the formula runs in NumPy float64 on the counts.  A NaN or an infinity raises
+        NumPy's ``ValueError("autodetected range of [..] is not finite")``, a range too narrow for ``nbins`` bins its ``ValueError("Too
+        many bins for data range...")``.
+    """
+    img = _real_plane(image)
+    nbins = operator.index(nbins)
+    if nbins < 1:
+        raise ValueError("`bins` must be positive, when an integer")          # NumPy's words
+    name = _np_name(img)
+    if name not in _HISTOGRAMMED:
+        raise NotImplementedError("threshold_otsu takes float32 / float64 and 8- / 16-bit integer images; got %s" % name)
+    dt = np.dtype(name)
+    height, width = img.shape
+    if height == 0 or width == 0:
+        raise ValueError("threshold_otsu of an empty image")
+    F.require_device()
+    lo, hi, bad = _minmax(img)
+    first, last = dt.type(lo), dt.type(hi)
+    if bad:
+        raise ValueError("autodetected range of [{}, {}] is not finite".format(first, last))
+    if first == last:
+        return first
+    if dt.kind == "f":
+        if nbins > 65536:
+            raise NotImplementedError("at most 65536 bins")
+        edges = np.linspace(first, last, nbins + 1, endpoint=True, dtype=dt)
+        if np.any(edges[:-1] >= edges[1:]):
+            raise ValueError(f'Too many bins for data range. Cannot create {nbins} finite-sized bins.')
+        counts = _histogram(img, nbins, edges=edges)
+        centres = (edges[:-1] + edges[1:]) / 2
+    else:
+        counts = _histogram(img, int(last) - int(first) + 1, first=int(first))
+        centres = np.arange(int(first), int(last) + 1)
+    return _otsu_of_counts(counts, centres)
+
+
+def _otsu_of_counts(counts, centres):
+    """The published Otsu formula on a histogram, in float64: the centre that maximises the between-class variance."""
+    c = counts.astype(np.float64)
+    w1 = np.cumsum(c)
+    w2 = np.cumsum(c[::-1])[::-1]
+    m1 = np.cumsum(c * centres) / w1
+    m2 = (np.cumsum((c * centres)[::-1]) / w2[::-1])[::-1]
+    v = w1[:-1] * w2[1:] * (m1[:-1] - m2[1:]) ** 2
+    return centres[np.argmax(v)]
+
+
+def clear_border(mat):
+    """
+    Set every 8-connected component of the nonzero pixels that touches the image border to 0: scikit-image's
+    ``clear_border(mat)`` for a binary image, restated as ``scipy.ndimage.label`` with the full 3 x 3 structure.
+
+    ``mat`` is a 2D NumPy array or torch tensor of any real element type; the result has its kind and dtype.  Only binary use is
+    promised; ``buffer_size``, ``bgval`` and ``mask`` are not taken.
+    """
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    mat, kind = _as_kind(mat)
+    img = _rows_image(mat)
+    if img.shape[0] == 0 or img.shape[1] == 0:
+        return mat.clone() if kind == "torch" else mat.copy()
+    F.require_device()
+    keep = _clear_border_plane(img)
+    if kind == "torch":
+        import torch
+        return torch.where(keep != 0, mat, torch.zeros_like(mat))
+    return np.where(keep != 0, mat, mat.dtype.type(0))
+
+
+def _cross_footprint(footprint):
+    if footprint is None:
+        return
+    fp = np.asarray(footprint)
+    if fp.shape != (3, 3) or not np.array_equal(fp != 0, _CROSS):
+        raise NotImplementedError("footprint must be None or the 3 x 3 cross (skimage.morphology.disk(1))")
+
+
+def opening(mat, footprint=None):
+    """
+    Morphological opening by the 3 x 3 cross: scikit-image's ``opening(mat, disk(1))``, restated as
+    ``scipy.ndimage.grey_opening(mat, footprint=cross, mode="reflect")`` (what lies outside the image is ignored).
+
+    ``mat`` is a 2D NumPy array or torch tensor: uint8 / bool of any values, or a 0 / 1 plane of any other real type (anything else
+    raises ``ValueError``).  ``footprint`` is None or the cross; another one raises ``NotImplementedError``.  The result has the
+    input's kind and dtype.
+    """
+    _cross_footprint(footprint)
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    mat, kind = _as_kind(mat)
+    img = _rows_image(mat)
+    if img.shape[0] == 0 or img.shape[1] == 0:
+        return mat.clone() if kind == "torch" else mat.copy()
+    F.require_device()
+    if _np_name(img) in ("uint8", "bool"):
+        res = _morph_plane(img, 2)
+        if _np_name(img) == "bool":
+            res = res != 0
+        return res
+    if not bool(((mat == 0) | (mat == 1)).all()):
+        raise ValueError("opening takes uint8 / bool images or 0 / 1 planes of another type")
+    mask = (mat != 0).to(_torch_uint8()) if kind == "torch" else (mat != 0).astype(np.uint8)
+    res = _morph_plane(_rows_image(mask), 2)
+    return res.to(mat.dtype) if kind == "torch" else res.astype(mat.dtype)
+
+
+def _torch_uint8():
+    import torch
+    return torch.uint8
+
+
+def _thres_double(thres, name):
+    """The double the threshold kernel compares with, for a threshold given against an image of NumPy type ``name`` as NumPy 2 compares
+    it: a Python number is weak (rounded to a float image's own type), a NumPy scalar promotes the comparison and is exact in it."""
+    if isinstance(thres, (bool, int, float)) and not isinstance(thres, np.generic) and np.dtype(name).kind == "f":
+        return float(np.dtype(name).type(thres))
+    return float(thres)
+
+
+def binarization(mat, ratio=0.3, thres=None, denoise=True):
+    """
+    Apply a list of operations: binarizing an 2D array; inverting the contrast of dots if needs to; removing border components;
+    cleaning salty noise; and filling holes (reference ``preprocessing.py:216-248``), every step on the GPU.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array (uploaded once; the result is downloaded once) or a ROCm torch tensor (every step on torch's
+        current stream).  float32 / float64 or an 8- / 16-bit integer type where ``thres`` is None.
+    ratio : float
+        Used to select the ROI around the middle of the image for calculating threshold.
+    thres : float, optional
+        Threshold for binarizing. Automatically calculated if None (:func:`threshold_otsu` of the ROI, 512 bins).
+    denoise : bool, optional
+        Apply denoising to the image if True (the 2 x 2 median of the absolute values).
+
+    Returns
+    -------
+    array_like
+        2D binary int16 array of the input's kind.  Feed it to ``get_points_dot_pattern(..., binarize=False)``.
+    """
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    mat, kind = _as_kind(mat)
+    if len(mat.shape) != 2:
+        raise ValueError("expected a 2-D array")
+    height, width = mat.shape
+    if height == 0 or width == 0:
+        if kind == "torch":
+            import torch
+            return torch.zeros((height, width), dtype=torch.int16, device=mat.device)
+        return np.zeros((height, width), np.int16)
+    if kind == "numpy":
+        host = _Image(mat, 2)          # (its checks, its byte order)
+        if thres is None and _np_name(host) not in _HISTOGRAMMED:
+            raise NotImplementedError("threshold_otsu takes float32 / float64 and 8- / 16-bit integer images; got %s" % _np_name(host))
+        F.require_device()
+        plane = _PlaneView(F.DeviceArray((height, width), host.dtype, host.device).copy_from_host(host.keep))
+    else:
+        if thres is None and str(mat.dtype).replace("torch.", "") not in _HISTOGRAMMED:
+            raise NotImplementedError("threshold_otsu takes float32 / float64 and 8- / 16-bit integer images; got %s" % mat.dtype)
+        F.require_device()
+        plane = mat
+
+    def view(a):
+        return a if kind == "torch" else _PlaneView(a)
+
+    if denoise:
+        plane = view(median_filter(view(_abs_plane(_rows_image(plane))), (2, 2)))
+    img = _rows_image(plane)
+    if thres is None:
+        thres = threshold_otsu(_select_roi(plane, ratio), nbins=512)
+    mask, count = _threshold_plane(img, _thres_double(thres, _np_name(img)))
+    mask = _clear_border_plane(_rows_image(mask), invert=2 * count > height * width)
+    mask = _morph_plane(_rows_image(mask), 2)
+    filled = binary_fill_holes(mask)
+    if kind == "torch":
+        import torch
+        return filled.to(torch.int16)
+    F.check(F.lib().dcp_stream_synchronize(img.device, img.stream))
+    return np.int16(filled.copy_to_host())

@@ -535,6 +535,56 @@ int dcp_label_measures_2d(const void* weights, const int32_t* labels, int height
 int dcp_fill_holes_2d(const void* src, uint8_t* dst, int height, int width, long src_row_stride, int dtype, int mem_kind, int device,
                       void* stream);
 
+/* ---- binarization of a dot image: absolute value, range, histogram, threshold, border components, 3 x 3-cross morphology ----
+ * discorpy/prep/preprocessing.py:216-248 (binarization) and what it calls: np.abs, skimage.filters.threshold_otsu (np.histogram /
+ * np.bincount), `mat > thres`, skimage.segmentation.clear_border, skimage.morphology.opening(mat, disk(1)).  Every entry takes src rows
+ * `src_row_stride` elements apart (>= width, unit column stride), a dense dst that does not overlap src, and the mem_kind / device /
+ * stream triple of dcp_label_2d (DCP_MEM_HOST: staged up and down by the library; DCP_MEM_DEVICE: enqueued on `stream`).
+ *
+ * dcp_abs_2d: dst = np.abs(src), same dtype, any DCP_DTYPE_*.  Floats lose their sign bit (a NaN's too), signed integers wrap at their
+ * minimum as NumPy's do, unsigned integers and bool are copied.
+ *
+ * dcp_minmax_2d: minmax_out[0] / [1] = src.min() / src.max() as NumPy returns them (NaN where any element is NaN), *nonfinite_out = the
+ * number of elements that are NaN or infinite.  DCP_DTYPE_FLOAT32 / FLOAT64 and the 8- / 16-bit integers (a double holds each value
+ * exactly).  Both outputs are HOST memory and THE CALL SYNCHRONISES `stream` BEFORE IT RETURNS, for device memory too.
+ *
+ * dcp_histogram_2d: counts_out[nbins] (HOST int64; the call synchronises `stream`).  Float planes, the edges form: `edges` = nbins + 1
+ * ascending HOST values of the plane's own type; bin i counts edges[i] <= a < edges[i + 1] and the last bin a == edges[nbins] too --
+ * np.histogram(a, nbins)'s counts when the edges are its own (np.linspace(a.min(), a.max(), nbins + 1)); elements outside
+ * [edges[0], edges[nbins]] and NaN are not counted; `first` is ignored.  8- / 16-bit integer planes, the bincount form: edges = NULL,
+ * bin a - first, elements outside [first, first + nbins) are not counted.  1 <= nbins <= 65536.  Up to 4096 bins a workgroup counts in LDS
+ * and flushes with 64-bit atomics, above that (or with the lab option "x_hist_lds" = 0) runs of equal bins add to global memory directly.
+ *
+ * dcp_threshold_2d: dst[y, x] = (double)src[y, x] > thres as a byte 0 / 1 (NaN compares false; 64-bit integers are rounded to double to
+ * nearest-even, as NumPy's cast does), any DCP_DTYPE_*.  `count` may be NULL; otherwise the number of set pixels is ADDED to *count, an
+ * int64 that lives where the planes live (device memory: the caller zeroes it on `stream`; no synchronisation).
+ *
+ * dcp_clear_border_2d: dst[y, x] = 1 where src is nonzero (invert = 1: where src is ZERO) and the component of such pixels that holds
+ * (y, x) -- connectivity 4 or 8 as for dcp_label_2d -- has no pixel in row 0, row height - 1, column 0 or column width - 1; else 0.
+ * skimage.segmentation.clear_border of a binary image (connectivity 8); invert = 1 clears the complement instead, so a contrast
+ * inversion needs no pass of its own.  The union-find, scratch (8 bytes per pixel) and lab option of dcp_fill_holes_2d.
+ *
+ * dcp_morph_cross_2d: grey erosion (op 0), dilation (op 1) or opening (op 2: erosion then dilation) of a uint8 plane by the 3 x 3 cross;
+ * what lies outside the image is ignored (minimum / maximum over the in-image neighbours only), which is both skimage's border rule and
+ * scipy.ndimage.grey_erosion / grey_dilation / grey_opening(footprint=cross, mode="reflect").  The opening is one launch (a 128 x 32
+ * tile with a halo of 2 in LDS); the lab option "x_morph_fused" = 0 makes it two, through a plane of scratch.
+ *
+ * All six: a null pointer, a height or width below 1, a stride below the width, an unknown dtype or mem_kind, src overlapping dst,
+ * nbins below 1, edges missing for a float plane or given for an integer one, a connectivity other than 4 or 8, an invert other than 0
+ * or 1 and an op outside 0..2 are DCP_ERR_INVALID_ARG; height * width above 2^31 - 1, a dtype the entry does not take and nbins above
+ * 65536 are DCP_ERR_UNSUPPORTED; all before any device call. */
+int dcp_abs_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, int mem_kind, int device, void* stream);
+int dcp_minmax_2d(const void* src, int height, int width, long src_row_stride, int dtype, double* minmax_out, int64_t* nonfinite_out,
+                  int mem_kind, int device, void* stream);
+int dcp_histogram_2d(const void* src, int height, int width, long src_row_stride, int dtype, const void* edges, int nbins, int64_t first,
+                     int64_t* counts_out, int mem_kind, int device, void* stream);
+int dcp_threshold_2d(const void* src, uint8_t* dst, int height, int width, long src_row_stride, int dtype, double thres, int64_t* count,
+                     int mem_kind, int device, void* stream);
+int dcp_clear_border_2d(const void* src, uint8_t* dst, int height, int width, long src_row_stride, int dtype, int connectivity, int invert,
+                        int mem_kind, int device, void* stream);
+int dcp_morph_cross_2d(const uint8_t* src, uint8_t* dst, int height, int width, long src_row_stride, int op, int mem_kind, int device,
+                       void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the

@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM traffic of the stack kernels by element type (tools/time_typed_stack.py, one launch per case): FETCH_SIZE and WRITE_SIZE in
-# separate rocprofv3 counter passes, converted as tools/summarize_prof.py does (KB; reads x 2 -- the calibration of tools/calib_copy.hip)
+# separate rocprofv3 counter passes, converted as tools/summarize_prof.py does (KB; reads x 2 -- the calibration of tools/attic/ubench/calib_copy.hip)
 # and set against the algorithmic bytes of the shard (2 x element size per voxel).   tools/pmc_typed_stack.sh [depth]
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 D=${1:-64}

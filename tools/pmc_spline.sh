@@ -2,7 +2,7 @@
 # HBM traffic of the launches of the cubic-spline path on a 4096^2 float32 frame (tools/time_spline.py --orders 3 --variants ${VARIANT:-1};
 # VARIANT=6: the three launches of rounds 3-5):
 # FETCH_SIZE and WRITE_SIZE in separate rocprofv3 counter passes (counters never together with --stats / trace domains other than
-# --kernel-trace), converted as tools/summarize_prof.py does (KB; reads x 2 -- the calibration of tools/calib_copy.hip, which is
+# --kernel-trace), converted as tools/summarize_prof.py does (KB; reads x 2 -- the calibration of tools/attic/ubench/calib_copy.hip, which is
 # re-run here on kernels that move exactly 1 GiB each way) and set against what each launch moves BY CONSTRUCTION.
 #   tools/pmc_spline.sh            (writes gpurun_out/pmc_spline.json + prints a table)
 case "${1:-}" in -h|--help) sed -n '2,7p' "$0" | sed 's/^# \{0,1\}//'; exit 0;; esac
@@ -14,7 +14,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/psp_$c /tmp/psc_$c
   (cd $ROOT && timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/psp_$c -o out -- python tools/time_spline.py --orders 3 --variants ${VARIANT:-1} --reps 12 > /tmp/psp_$c.log 2>&1)
 done
-hipcc --offload-arch=gfx950 -O3 -o /tmp/calib_copy $ROOT/tools/calib_copy.hip > /tmp/psc_build.log 2>&1
+hipcc --offload-arch=gfx950 -O3 -o /tmp/calib_copy $ROOT/tools/attic/ubench/calib_copy.hip > /tmp/psc_build.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/psc_$c -o out -- /tmp/calib_copy > /tmp/psc_$c.log 2>&1
 done
