@@ -9,18 +9,22 @@ The conditions under which these ARE yardsticks are asserted by tests/test_binar
 "ignore what lies outside" (``pad_and_ignore``), and np.histogram equals the plain search of its own edges (``histogram_by_search``)
 although its raw estimate (``raw_estimate``) is off by one for many elements of the edge-hugging inputs.
 
-The shapes come from the kernels' tiles (SHAPES), pinned to dcp_internal.h by tests/test_binarize_cpu.py.
+The shapes come from the kernels' tiles (SHAPES), pinned to dcp_internal.h by tests/test_binarize_cpu.py; MEDIUM and LARGE are those of
+tests/helpers/label_cases.py, where they are explained.
 """
 import functools
 
 import numpy as np
 from scipy import ndimage as ndi
 
+from label_cases import LARGE, MEDIUM  # noqa: F401
+
 CROSS = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
 BLOCK = np.ones((3, 3), bool)
 TILE = {"TH": 32, "TW": 128}          # kMorphTH / kMorphTW (and kLabelTH / kLabelTW)
 TH, TW = TILE["TH"], TILE["TW"]
 HIST_LDS_MAX_BINS = 4096               # kHistLdsMaxBins
+REDUCE_MAX_BLOCKS, BIN_BLOCK = 1024, 256          # kReduceMaxBlocks, kBinBlock: the grid of minmax_kernel / histogram_kernel
 SHAPES = [(1, 1), (1, 2 * TW + 3), (2 * TH + 3, 1), (TH, TW), (TH + 1, TW + 1), (2 * TH + 5, 3 * TW + 7)]
 HIST_DTYPES = ("float32", "float64", "uint8", "int8", "uint16", "int16")
 

@@ -3,6 +3,14 @@
 TILE is label_tile_kernel's tile as the tests assume it; tests/test_label_cpu.py pins it to kLabelTH / kLabelTW of
 discorpy_amd/csrc/dcp_internal.h.  Every shape is built from it: a single pixel, a row and a column that span three tiles, exactly one
 tile, one pixel more each way (four tiles, three of them slivers), and a frame of 3 x 4 tiles with ragged edges.
+
+MEDIUM and LARGE are for tests/test_label_scale_gpu.py and tests/test_binarize_scale_gpu.py.  MEDIUM is 6 x 5 ragged tiles: about 330
+workgroups of pair threads under "x_label_lds" 0, small enough for the long chains of the adversarial patterns.  LARGE is the smallest
+kind of frame at which the loops that SHAPES never turns do turn: label_scan_kernel walks three rounds of kLabelBlock block counts (the
+carry between rounds, and the sums of earlier waves within one), minmax_kernel and histogram_kernel reach their cap of kReduceMaxBlocks
+workgroups with a last round that is ragged between workgroups, and the sums of 16-bit weights stay below 2^53, where scipy's float64
+accumulation is still exact.  tests/test_label_cpu.py and tests/test_binarize_cpu.py assert every one of these conditions against the
+kernels' constants.
 """
 import functools
 
@@ -12,10 +20,29 @@ TILE = {"TH": 32, "TW": 128}
 TH, TW = TILE["TH"], TILE["TW"]
 SHAPES = [(1, 1), (1, 2 * TW + 3), (2 * TH + 3, 1), (TH, TW), (TH + 1, TW + 1), (2 * TH + 5, 3 * TW + 7)]
 BIG = SHAPES[-1]
+MEDIUM = (5 * TH + 3, 4 * TW + 5)
+LARGE = (1103, 2303)
 CROSS = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
 BLOCK = np.ones((3, 3), bool)
 STRUCTURES = {4: CROSS, 8: BLOCK}
 DENSITIES = (0.3, 0.55, 0.6, 0.8)
+
+
+def large_conditions(shape, scan_chunk, label_block, reduce_max_blocks, bin_block):
+    """What makes ``shape`` a LARGE, as a dict of named conditions, given kLabelScanChunk, kLabelBlock, kReduceMaxBlocks and kBinBlock."""
+    h, w = shape
+    n = h * w
+    nb = -(-n // scan_chunk)
+    return {
+        "ragged tile, wider than a wave": h % TH != 0 and w % TW > 64,
+        "no row and no plane of whole quads": w % 4 != 0 and n % 4 != 0,
+        "three scan rounds, two of them full": nb > 2 * label_block,
+        "the partial scan round crosses a wave": nb % label_block > 64,
+        "the cap of the reduce grid is reached": -(-n // (bin_block * 8)) > reduce_max_blocks,
+        "the last reduce round is ragged between workgroups": n % (reduce_max_blocks * bin_block) >= bin_block,
+        "float64 sums of 16-bit weights are exact": n * max(h, w) * 65535 < 2**53,
+        "below 2^24 pixels": n < 2**24,
+    }
 
 
 def zeros(h, w):
@@ -154,11 +181,12 @@ def diagonal_gap(h, w):
     m[0::20, 0::10] = 0
     m[10::20, 0::10] = 0
     m[10::20, 1::10] = 0
-    y, x = np.mgrid[0:h, 0:w]
+    dy, dx = np.mgrid[-4:5, -4:5]
+    diamond = np.abs(dy) + np.abs(dx) == 4
     for cy in range(14, h - 4, 30):
         for cx in range(24, w - 4, 30):
             m[cy - 5:cy + 6, cx - 5:cx + 6] = 0
-            m[np.abs(y - cy) + np.abs(x - cx) == 4] = 1
+            m[cy - 4:cy + 5, cx - 4:cx + 5][diamond] = 1          # (the window lies inside the frame: 4 <= cy < h - 4, cx likewise)
     return m
 
 

@@ -123,6 +123,23 @@ def test_tile_table_of_the_gpu_tests_is_the_kernels():
     m = re.search(r"constexpr int kHistLdsMaxBins = (\d+);", text)
     assert m and int(m.group(1)) == bref.HIST_LDS_MAX_BINS
     assert 256 < bref.HIST_LDS_MAX_BINS < 65536          # 8-bit counts stay below the switch, 16-bit ones can stand on both sides
+    # LARGE and MEDIUM are the labelling tests'; what LARGE promises about minmax_kernel's and histogram_kernel's grid, from the constants
+    assert (bref.LARGE, bref.MEDIUM) == (cases.LARGE, cases.MEDIUM)
+    found = {}
+    for name, source in (("kLabelScanChunk", "dcp_internal.h"), ("kReduceMaxBlocks", "dcp_internal.h"), ("kLabelBlock", "label_kernels.hip"),
+                         ("kBinBlock", "binarize_kernels.hip")):
+        m = re.search(r"^constexpr int %s = (\d+);" % name, open(os.path.join(ROOT, "discorpy_amd", "csrc", source)).read(), re.M)
+        assert m, "%s is not a named constant of %s" % (name, source)
+        found[name] = int(m.group(1))
+    held = cases.large_conditions(bref.LARGE, found["kLabelScanChunk"], found["kLabelBlock"], found["kReduceMaxBlocks"], found["kBinBlock"])
+    assert len(held) == 8 and all(held.values()), [k for k, v in held.items() if not v]
+    cap, block, n = found["kReduceMaxBlocks"], found["kBinBlock"], bref.LARGE[0] * bref.LARGE[1]
+    assert (cap, block) == (bref.REDUCE_MAX_BLOCKS, bref.BIN_BLOCK)
+    assert re.search(r"const int64_t want = \(n \+ kBinBlock \* 8 - 1\) / \(kBinBlock \* 8\);", open(os.path.join(ROOT, "discorpy_amd", "csrc",
+                                                                                                          "binarize_kernels.hip")).read())
+    rounds = -(-n // (cap * block))
+    assert rounds == 10 and (cap - 1) * block + (rounds - 1) * cap * block >= n          # the last workgroup walks one round fewer
+    assert 0 < n - (rounds - 1) * cap * block < cap * block and (n - (rounds - 1) * cap * block) % block != 0          # and one is cut short
 
 
 # ---------------------------------------------------------------------------------------------- the yardstick

@@ -147,6 +147,18 @@ def test_lab_option_round_trips_under_its_prefixed_name_only():
         F.set_option("label_lds", 0)
 
 
+def kernel_constants():
+    """kLabelScanChunk and kReduceMaxBlocks of dcp_internal.h, kLabelBlock and kBinBlock of the two kernel files."""
+    csrc = os.path.join(ROOT, "discorpy_amd", "csrc")
+    found = {}
+    for name, source in (("kLabelScanChunk", "dcp_internal.h"), ("kReduceMaxBlocks", "dcp_internal.h"), ("kLabelBlock", "label_kernels.hip"),
+                         ("kBinBlock", "binarize_kernels.hip")):
+        m = re.search(r"^constexpr int %s = (\d+);" % name, open(os.path.join(csrc, source)).read(), re.M)
+        assert m, "%s is not a named constant of %s" % (name, source)
+        found[name] = int(m.group(1))
+    return found
+
+
 def test_tile_table_of_the_gpu_tests_is_the_kernels():
     text = open(os.path.join(ROOT, "discorpy_amd", "csrc", "dcp_internal.h")).read()
     m = re.search(r"constexpr int kLabelTW = (\d+), kLabelTH = (\d+);", text)
@@ -154,6 +166,25 @@ def test_tile_table_of_the_gpu_tests_is_the_kernels():
     assert (int(m.group(2)), int(m.group(1))) == (cases.TILE["TH"], cases.TILE["TW"])
     th, tw = cases.TH, cases.TW
     assert cases.SHAPES == [(1, 1), (1, 2 * tw + 3), (2 * th + 3, 1), (th, tw), (th + 1, tw + 1), (2 * th + 5, 3 * tw + 7)]
+    assert cases.BIG == cases.SHAPES[-1] and cases.MEDIUM == (5 * th + 3, 4 * tw + 5) == (163, 517)
+    # LARGE turns the loops of label_scan_kernel, minmax_kernel and histogram_kernel that the shapes above never turn
+    const = kernel_constants()
+    assert const == {"kLabelScanChunk": 4096, "kLabelBlock": 256, "kReduceMaxBlocks": 1024, "kBinBlock": 256}, "a constant moved: derive LARGE again"
+    args = (const["kLabelScanChunk"], const["kLabelBlock"], const["kReduceMaxBlocks"], const["kBinBlock"])
+    held = cases.large_conditions(cases.LARGE, *args)
+    assert len(held) == 8 and all(held.values()), [k for k, v in held.items() if not v]
+    n = cases.LARGE[0] * cases.LARGE[1]
+    assert (n, -(-n // const["kLabelScanChunk"])) == (2540209, 621)
+    # the conditions tell: each of these frames misses what is named and nothing else (with these constants three scan rounds and the
+    # capped grid both begin above 2^21 pixels)
+    scan, cap = "three scan rounds, two of them full", "the cap of the reduce grid is reached"
+    for shape, missed in (((601, 4099), ["ragged tile, wider than a wave"]), ((600, 4095), ["no row and no plane of whole quads"]),
+                          ((601, 2303), [scan, cap]), ((745, 4223), ["the partial scan round crosses a wave"]),
+                          ((807, 4223), ["the last reduce round is ragged between workgroups"]),
+                          ((601, 16511), ["float64 sums of 16-bit weights are exact"]), ((4099, 4223), ["below 2^24 pixels"])):
+        got = cases.large_conditions(shape, *args)
+        assert [k for k, v in got.items() if not v] == missed, (shape, missed)
+    assert not cases.large_conditions(cases.BIG, *args)[scan] and not cases.large_conditions(cases.BIG, *args)[cap]
 
 
 # ---------------------------------------------------------------------------------------------- the Python functions

@@ -168,7 +168,7 @@ def test_kernels_launched_under_each_option_value(prep, hip):
 # ---------------------------------------------------------------------------------------------- measurements
 
 def weights(dtype, shape, seed):
-    """Values over the whole range of the type (negative ones for int16), zero included."""
+    """Values over the whole range of the type (negative ones for int8 and int16), zero included."""
     rng = np.random.default_rng(seed)
     dt = np.dtype(dtype)
     if dt.kind == "b":
@@ -190,7 +190,7 @@ def check_measures(prep, mat, labels, index):
         assert type(got_com[0]) is tuple and len(got_com[0]) == 2
 
 
-@pytest.mark.parametrize("dtype", ["bool", "uint8", "int16", "uint16"])
+@pytest.mark.parametrize("dtype", ["bool", "uint8", "int8", "int16", "uint16"])
 def test_measures_equal_scipys(prep, dtype):
     for k, density in enumerate(cases.DENSITIES):
         name = "random_%g" % density
@@ -206,7 +206,7 @@ def test_measures_equal_scipys(prep, dtype):
         assert prep.find_objects(labels, max(num - 1, 1)) == ndi.find_objects(labels, max(num - 1, 1))
 
 
-@pytest.mark.parametrize("dtype", ["bool", "uint8", "int16", "uint16"])
+@pytest.mark.parametrize("dtype", ["bool", "uint8", "int8", "int16", "uint16"])
 def test_one_component_that_spans_the_image(prep, dtype):
     labels = np.ones(BIG, np.int32)
     mat = weights(dtype, BIG, 700)
