@@ -159,7 +159,7 @@ struct WorkspaceLease {
 static_assert(DCP_MAP_RADIAL == dcp::kRadial && DCP_MAP_PERSPECTIVE == dcp::kPersp && DCP_MAP_FUSED == dcp::kFused, "map kinds");
 
 // One description of every single-frame call (api_image.cpp make_frame_call validates it, run_frame executes it), as StackCall
-// is of every stack call.  Executors: the tuned float32 kernels within 32-bit offsets (unwarp_kernels.hip), the generic ones for
+// is of every stack call and PlaneCall (api_plane.h) of every plane call, the dcp_*_2d filters and labellings of prep.  Executors: the tuned float32 kernels within 32-bit offsets (unwarp_kernels.hip), the generic ones for
 // orders 0 / 1 on any element type (typed_kernels.hip, or remap_wg_kernel / the one-channel colour kernel where they qualify),
 // interleaved channels (color_kernels.hip), spline orders 2..5 (api_spline.cpp, spline_kernels.hip), the forward scatter of any element
 // type (api_spline.cpp for its winner plane, forward_kernels.hip), interleaved channels at spline orders 2..5 (api_spline.cpp,
@@ -226,12 +226,6 @@ int host_round_trip(const HostTrip& t, hipStream_t st, Launch&& launch) {
   DCP_HIP(hipStreamSynchronize(st));
   return DCP_OK;
 }
-
-// api_label.cpp: the checks the plane entry points share (labelling, hole filling, binarization), before any device call; dst_elem = 0:
-// the call has no destination plane.  *host = DCP_MEM_HOST
-int check_plane_call(const void* src, const void* dst, int height, int width, long src_row_stride, int dtype, size_t dst_elem, int mem_kind, bool* host);
-// api_label.cpp: the round trip of such a call -- the rows packed on the way up, height * width * dst_elem bytes back (none without dst)
-HostTrip packed_rows(const void* src, void* dst, int height, int width, long src_row_stride, size_t esz, size_t dst_elem);
 
 // api_spline.cpp: the spline executor (c.exec == kExecSpline; the device is selected)
 int run_spline(const FrameCall& c);

@@ -28,8 +28,8 @@ import numbers
 import numpy as np
 
 from .. import _ffi as F
-from ..post.postprocessing import _Image, _MODES, _is_cai, _is_torch, remap_coordinates
-from .preprocessing import _is_complex
+from ..post.postprocessing import _Image, _MODES, remap_coordinates
+from .preprocessing import _as_kind, _is_complex, _row_stride, _rows_image
 
 __all__ = ["gaussian_filter", "convert_chessboard_to_linepattern", "get_tilted_profile"]
 
@@ -97,20 +97,16 @@ def gaussian_filter(mat, sigma, *, order=0, mode="reflect", cval=0.0, truncate=4
     if img.code == F.DTYPE_BY_NAME["bool"]:
         raise RuntimeError("data type not supported")
     weights = [_gaussian_weights(s, truncate, r) if s > 1e-15 else None for s, r in zip(sigmas, radii)]
-    if img.strides[1] != 1 and img.shape[1] > 1 or img.strides[0] < img.shape[1] and img.shape[0] > 1:
-        if img.cai:
-            raise ValueError("device arrays must have unit column stride and non-overlapping rows")
-        img = _Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 2)
+    img = _rows_image(img)
     height, width = img.shape
     res, optr = img.empty((height, width), out=out)
     if height == 0 or width == 0:
         return res
     F.require_device()
-    row_stride = img.strides[0] if height > 1 else width          # (a single row's stride is arbitrary)
     wargs = []
     for w in weights:
         wargs += [None, -1] if w is None else [w.ctypes.data_as(F.C.POINTER(F.C.c_double)), len(w) // 2]
-    F.check(F.lib().dcp_correlate_sym_2d(img.ptr, optr, height, width, row_stride, img.code, *wargs, _MODES.index(mode), float(cval),
+    F.check(F.lib().dcp_correlate_sym_2d(img.ptr, optr, height, width, _row_stride(img), img.code, *wargs, _MODES.index(mode), float(cval),
                                          img.mem, img.device, img.stream))
     return res
 
@@ -139,10 +135,11 @@ def convert_chessboard_to_linepattern(mat, smooth=True, bgr="bright", sigma=3):
         it); the mean is then a reduction in another order, so the result agrees to rounding; a tensor is returned.
     """
     crop = 4 if smooth is True else 2
-    if _is_torch(mat) and mat.is_cuda:
+    mat, kind = _as_kind(mat, "convert_chessboard_to_linepattern takes NumPy arrays and torch tensors; use gaussian_filter for other device arrays")
+    if smooth is True:
+        mat = gaussian_filter(mat, sigma, mode="nearest")
+    if kind == "torch":
         import torch
-        if smooth is True:
-            mat = gaussian_filter(mat, sigma, mode="nearest")
         if not mat.is_floating_point():
             mat = mat.to(torch.float64)
         grad_y, grad_x = torch.gradient(mat)
@@ -152,11 +149,6 @@ def convert_chessboard_to_linepattern(mat, smooth=True, bgr="bright", sigma=3):
         if bgr == "bright":
             mat_line = mat_line.max() - mat_line
         return mat_line / mat_line.abs().mean()
-    if _is_cai(mat):
-        raise TypeError("convert_chessboard_to_linepattern takes NumPy arrays and torch tensors; use gaussian_filter for other device arrays")
-    mat = np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat)
-    if smooth is True:
-        mat = gaussian_filter(mat, sigma, mode="nearest")
     mat_line = np.mean(np.abs(np.gradient(mat)), axis=0)
     mat_line = np.pad(mat_line[crop:-crop, crop:-crop], crop, mode="edge")
     if bgr == "bright":

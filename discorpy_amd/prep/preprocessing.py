@@ -91,6 +91,38 @@ def _is_complex(mat):
     return np.asarray(mat).dtype.kind == "c"
 
 
+def _as_kind(mat, refusal="takes NumPy arrays and torch tensors"):
+    """(``mat`` as the array the steps work on, "torch" / "numpy"): a ROCm tensor stays, a CPU tensor or an array-like becomes a NumPy
+    array, any other device array is a ``TypeError`` of the text ``refusal``."""
+    if _is_torch(mat) and mat.is_cuda:
+        return mat, "torch"
+    if _is_cai(mat):
+        raise TypeError(refusal)
+    return np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat), "numpy"
+
+
+def _rows_image(mat):
+    """``mat`` (or the :class:`_Image` of it) as a 2-D :class:`_Image` with unit column stride and non-overlapping rows (a copy where it
+    is not)."""
+    img = mat if isinstance(mat, _Image) else _Image(mat, 2)
+    if img.strides[1] != 1 and img.shape[1] > 1 or img.strides[0] < img.shape[1] and img.shape[0] > 1:
+        if img.cai:
+            raise ValueError("device arrays must have unit column stride and non-overlapping rows")
+        img = _Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 2)
+    return img
+
+
+def _row_stride(img):
+    return img.strides[0] if img.shape[0] > 1 else img.shape[1]          # (a single row's stride is arbitrary)
+
+
+def _real_plane(mat):
+    """``mat`` as a 2-D :class:`_Image` of a real element type (the module's ``TypeError`` for complex input)."""
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    return _rows_image(mat)
+
+
 def median_filter(mat, size, *, out=None):
     """
     2-D median filter with scipy's ``mode="reflect"``: ``scipy.ndimage.median_filter(mat, size, mode="reflect")`` on the GPU.
@@ -114,18 +146,13 @@ def median_filter(mat, size, *, out=None):
     if _is_complex(mat):
         raise TypeError("Complex type not supported")
     sy, sx = _window(size)
-    img = _Image(mat, 2)
-    if img.strides[1] != 1 and img.shape[1] > 1 or img.strides[0] < img.shape[1] and img.shape[0] > 1:
-        if img.cai:
-            raise ValueError("device arrays must have unit column stride and non-overlapping rows")
-        img = _Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 2)
+    img = _rows_image(mat)
     height, width = img.shape
     res, optr = img.empty((height, width), out=out)
     if height == 0 or width == 0:
         return res
     F.require_device()
-    row_stride = img.strides[0] if height > 1 else width          # (a single row's stride is arbitrary)
-    F.check(F.lib().dcp_median_filter_2d(img.ptr, optr, height, width, row_stride, img.code, sy, sx, img.mem, img.device, img.stream))
+    F.check(F.lib().dcp_median_filter_2d(img.ptr, optr, height, width, _row_stride(img), img.code, sy, sx, img.mem, img.device, img.stream))
     return res
 
 
@@ -148,16 +175,13 @@ def normalization(mat, size=51):
         the median plane is computed on torch's current stream, its mean is taken in float64 and rounded to the result type
         (the input's for floats, float64 otherwise) and the quotient is computed with torch; a tensor is returned.
     """
-    if _is_torch(mat) and mat.is_cuda:
+    mat, kind = _as_kind(mat, "normalization takes NumPy arrays and torch tensors; use median_filter for other device arrays")
+    mat_bck = median_filter(mat, size)
+    if kind == "torch":
         import torch
-        mat_bck = median_filter(mat, size)
         rtype = mat.dtype if mat.is_floating_point() else torch.float64
         mean_val = mat_bck.to(torch.float64).mean().to(rtype)
         return mean_val * mat.to(rtype) / mat_bck.to(rtype)
-    if _is_cai(mat):
-        raise TypeError("normalization takes NumPy arrays and torch tensors; use median_filter for other device arrays")
-    mat = np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat)
-    mat_bck = median_filter(mat, size)
     mean_val = np.mean(mat_bck)
     try:
         mat_cor = mean_val * mat / mat_bck
@@ -171,20 +195,6 @@ def normalization(mat, size=51):
 
 _CROSS = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
 _MEASURED = ("bool", "uint8", "int8", "uint16", "int16")
-
-
-def _rows_image(mat):
-    """``mat`` as a 2-D :class:`_Image` with unit column stride and non-overlapping rows (a copy where it is not)."""
-    img = _Image(mat, 2)
-    if img.strides[1] != 1 and img.shape[1] > 1 or img.strides[0] < img.shape[1] and img.shape[0] > 1:
-        if img.cai:
-            raise ValueError("device arrays must have unit column stride and non-overlapping rows")
-        img = _Image(img.keep.contiguous() if img.torch else np.ascontiguousarray(img.keep), 2)
-    return img
-
-
-def _row_stride(img):
-    return img.strides[0] if img.shape[0] > 1 else img.shape[1]          # (a single row's stride is arbitrary)
 
 
 def _new_like(img, shape, dtype):
@@ -275,9 +285,7 @@ def binary_fill_holes(mat):
         2D bool array of the input's kind: the nonzero pixels and every region of zeros that reaches no border through its
         4-neighbours.
     """
-    if _is_complex(mat):
-        raise TypeError("Complex type not supported")
-    img = _rows_image(mat)
+    img = _real_plane(mat)
     height, width = img.shape
     res, rptr = _new_like(img, (height, width), np.bool_)
     if height == 0 or width == 0:
@@ -469,14 +477,12 @@ def _binary_mask(mat):
     """uint8 mask of a 0 / 1 image of any dtype and kind; the reference's check (``preprocessing.py:991-993``) and its message, applied
     to every value."""
     msg = "Input not a binary image, e.i. maximum_value=1 and minimum value=0!!!"
-    if _is_torch(mat) and mat.is_cuda:
+    mat, kind = _as_kind(mat, "takes NumPy arrays and torch tensors; label other device arrays with label()")
+    if kind == "torch":
         import torch
         if mat.numel() == 0 or mat.max() != 1.0 or mat.min() != 0.0 or not bool(((mat == 0) | (mat == 1)).all()):
             raise ValueError(msg)
         return (mat != 0).to(torch.uint8)
-    if _is_cai(mat):
-        raise TypeError("takes NumPy arrays and torch tensors; label other device arrays with label()")
-    mat = np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat)
     if np.max(mat) != 1.0 or np.min(mat) != 0.0:
         raise ValueError(msg)
     if not np.all((mat == 0) | (mat == 1)):
@@ -503,11 +509,8 @@ def get_points_dot_pattern(mat, binarize=True, ratio=0.3, thres=None):
 
 
 def _host_array(mat):
-    if _is_torch(mat):
-        return mat.detach().cpu().numpy()
-    if _is_cai(mat):
-        raise TypeError("takes NumPy arrays and torch tensors")
-    return np.asarray(mat)
+    mat, kind = _as_kind(mat)
+    return mat.detach().cpu().numpy() if kind == "torch" else mat
 
 
 def select_dots_based_size(mat, dot_size, ratio=0.3):
@@ -593,13 +596,6 @@ class _PlaneView:
         return view
 
 
-def _real_plane(mat):
-    """``mat`` as a 2-D :class:`_Image` of a real element type (the module's ``TypeError`` for complex input)."""
-    if _is_complex(mat):
-        raise TypeError("Complex type not supported")
-    return _rows_image(mat)
-
-
 def _abs_plane(img):
     """``np.abs`` of the plane of ``img`` (an :class:`_Image`) as a fresh array of its kind; unsigned and bool planes come back as they are."""
     if np.dtype(_np_name(img)).kind in "ub":
@@ -642,12 +638,10 @@ def _threshold_plane(img, thres):
     """(uint8 plane of ``(double)a > thres`` of the kind of ``img``, the exact number of set pixels).  Waits for the image's stream."""
     height, width = img.shape
     mask, mptr = _new_like(img, (height, width), np.uint8)
-    if img.mem == F.MEM_HOST:
-        count = ctypes.c_int64(0)
-        F.check(F.lib().dcp_threshold_2d(img.ptr, mptr, height, width, _row_stride(img), img.code, float(thres), ctypes.addressof(count), img.mem,
-                                         img.device, img.stream))
-        return mask, int(count.value)
-    if img.torch:
+    if img.mem == F.MEM_HOST:          # the count is a word of the memory the plane is in
+        count = np.zeros(1, np.int64)
+        cptr = count.ctypes.data
+    elif img.torch:
         import torch
         count = torch.zeros(1, dtype=torch.int64, device=img.keep.device)
         cptr = count.data_ptr()
@@ -673,15 +667,6 @@ def _morph_plane(img, op):
     res, rptr = _new_like(img, (height, width), np.uint8)
     F.check(F.lib().dcp_morph_cross_2d(img.ptr, rptr, height, width, _row_stride(img), op, img.mem, img.device, img.stream))
     return res
-
-
-def _as_kind(mat):
-    """(``mat`` as the array the steps work on, "torch" / "numpy"): a ROCm tensor stays, anything else becomes a NumPy array."""
-    if _is_torch(mat) and mat.is_cuda:
-        return mat, "torch"
-    if _is_cai(mat):
-        raise TypeError("takes NumPy arrays and torch tensors")
-    return np.asarray(mat.detach().cpu().numpy() if _is_torch(mat) else mat), "numpy"
 
 
 def _select_roi(mat, ratio, square=False):
@@ -838,14 +823,10 @@ def opening(mat, footprint=None):
         return res
     if not bool(((mat == 0) | (mat == 1)).all()):
         raise ValueError("opening takes uint8 / bool images or 0 / 1 planes of another type")
-    mask = (mat != 0).to(_torch_uint8()) if kind == "torch" else (mat != 0).astype(np.uint8)
-    res = _morph_plane(_rows_image(mask), 2)
-    return res.to(mat.dtype) if kind == "torch" else res.astype(mat.dtype)
-
-
-def _torch_uint8():
-    import torch
-    return torch.uint8
+    if kind == "torch":
+        import torch
+        return _morph_plane(_rows_image((mat != 0).to(torch.uint8)), 2).to(mat.dtype)
+    return _morph_plane(_rows_image((mat != 0).astype(np.uint8)), 2).astype(mat.dtype)
 
 
 def _thres_double(thres, name):

@@ -47,6 +47,70 @@ def f64(v):
     return np.asarray(v, dtype=np.float64)
 
 
+# ---- plane_refusals.json: what every refused argument of the plane entry points (dcp_*_2d of api_median / api_gauss / api_label /
+# api_binarize.cpp) is answered with TODAY: the return code and the whole of dcp_last_error(), for every case of the tables of
+# tests/test_{median,gaussian,label,binarize}_cpu.py (those match a fragment of the message only).  Run it with the library the
+# recording is to pin, before a change to the argument checks -- not after, to make a failing replay pass:
+#     python tools/gen_golden.py --plane-refusals
+# Pointers are recorded by name ("null", "src", "dst", "src+166": bytes into the source buffer, the caller's outputs under their key);
+# tests/test_plane_refusals_cpu.py builds buffers of the same sizes and replays the calls.
+def plane_refusals():
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_binarize_cpu as tb
+    import test_gaussian_cpu as tg
+    import test_label_cpu as tl
+    import test_median_cpu as tm
+    from discorpy_amd import _ffi as F
+
+    def encode(mod, key, v):
+        if v is None:
+            return "null"
+        if isinstance(v, np.ndarray):          # weights of the Gaussian
+            return {"repeat": float(v[0]), "n": len(v)} if len(v) > 8 and (v == v[0]).all() else [float(x) for x in v]
+        if key in ("src", "dst", "weights", "labels"):
+            for name, buf in (("src", mod.SRC), ("dst", mod.DST)):
+                off = v - buf.ctypes.data
+                if 0 <= off < buf.nbytes:
+                    return name if off == 0 else "%s+%d" % (name, off)
+            raise ValueError((key, v))
+        if key in ("num", "sums", "boxes", "minmax", "bad", "counts", "count", "edges"):
+            return key                          # the caller's outputs and the edges: the buffer of that name
+        assert isinstance(v, (int, float)), (key, v)
+        return v
+
+    entries, cases = {}, []
+
+    def record(mod, symbol, valid, order, table, call):
+        entries[symbol] = {"order": order, "valid": {k: encode(mod, k, valid[k]) for k in order}}
+        for override, rc, fragment in table:
+            got = call(override)
+            msg = F.last_error()
+            assert got == rc and fragment in msg, (symbol, override, got, msg)
+            cases.append({"entry": symbol, "override": {k: encode(mod, k, v) for k, v in sorted(override.items())}, "code": got, "message": msg})
+
+    record(tm, "dcp_median_filter_2d", tm.VALID, tm.ORDER, tm.CASES, lambda o: tm.call(**o))
+    record(tg, "dcp_correlate_sym_2d", tg.VALID, tg.ORDER, tg.CASES, lambda o: tg.call(**o))
+    record(tl, "dcp_label_2d", tl.LABEL, tl.LABEL_ORDER, tl.LABEL_CASES, lambda o: tl.call("dcp_label_2d", tl.LABEL, tl.LABEL_ORDER, o))
+    last = tl.SRC.ctypes.data + 2 * ((tl.H - 1) * (tl.W + 4) + tl.W)          # dst is bytes there: its first one on the source's last
+    fill = [(dict(o, dst=last - 1) if o.get("dst") == last - 2 else o, rc, frag) for o, rc, frag in tl.SHARED]
+    record(tl, "dcp_fill_holes_2d", tl.FILL, tl.FILL_ORDER, fill, lambda o: tl.call("dcp_fill_holes_2d", tl.FILL, tl.FILL_ORDER, o))
+    record(tl, "dcp_label_measures_2d", tl.MEAS, tl.MEAS_ORDER, tl.MEAS_CASES, lambda o: tl.call("dcp_label_measures_2d", tl.MEAS, tl.MEAS_ORDER, o))
+    for symbol, (valid, order) in tb.CALLS.items():
+        record(tb, symbol, valid, order, [c[1:] for c in tb.REFUSALS if c[0] == symbol], lambda o, symbol=symbol: tb.call(symbol, o))
+    assert not any("0x" in c["message"] for c in cases), "a message carries an address: mask it"
+    path = os.path.join(OUT, "plane_refusals.json")
+    with open(path, "w") as f:
+        json.dump({"entries": entries, "cases": cases}, f, indent=1)
+        f.write("\n")
+    print("plane_refusals.json  %d cases of %d entry points" % (len(cases), len(entries)))
+
+
+if "--plane-refusals" in sys.argv[1:]:
+    plane_refusals()
+    raise SystemExit(0)
+
+
 # ---- G1: the reference's own unwarp_image_backward test input (tests/test_postprocessing.py:77-85)
 hei = wid = 64
 mat = np.zeros((hei, wid), dtype=np.float32)
