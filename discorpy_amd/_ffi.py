@@ -115,6 +115,7 @@ SIGNATURES = {
                                        _int, _vp]),
     "dcp_median_filter_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _int, _vp]),
     "dcp_correlate_sym_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _dp, _int, _dp, _int, _int, _dbl, _int, _int, _vp]),
+    "dcp_fourier_gauss_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _dp, _dp, _dp, _dp, _int, _int, _vp]),
     "dcp_label_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, C.POINTER(_int), _int, _int, _vp]),
     "dcp_label_measures_2d": (_int, [_vp, _vp, _int, _int, C.c_long, C.c_long, _int, _int, _vp, _vp, _int, _int, _vp]),
     "dcp_fill_holes_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),

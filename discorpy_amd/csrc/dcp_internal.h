@@ -201,6 +201,7 @@ hipError_t read_bounds_spline_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_frames(unsigned long long* out, bool reset);
 hipError_t read_bounds_gauss(unsigned long long* out, bool reset);
 hipError_t read_bounds_label(unsigned long long* out, bool reset);
+hipError_t read_bounds_fourier(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -284,6 +285,17 @@ constexpr int kGaussFusedMaxLds = 80 << 10;  // this many bytes of LDS, two work
 bool gauss_takes_lds(int dtype, int ry, int rx, int lds_mode);
 hipError_t launch_gauss(const void* src, void* dst, void* tmp, int H, int W, int64_t src_stride, int dtype, const double* wy, int ry,
                         const double* wx, int rx, int boundary, double cval, int lds_mode, hipStream_t stream);
+// fourier_kernels.hip: the Fourier Gaussian filter of _apply_fft_filter as two Toeplitz passes in float64: dst (dense H x W doubles) from
+// the H x W plane at src (any ElemType, rows `src_stride` elements apart) padded by `pad` under `boundary` (np.pad's mode as a
+// BoundaryMode: kModeMirror "reflect", kModeReflect "symmetric", kModeNearest "edge", kModeWrap "wrap", kModeConstant zeros).
+// taps = {y re, y im, x re, x im}: HOST arrays of 2 N - 1 doubles, N the padded side of the axis; ry / rx: the support radius per axis
+// (only |d| <= r and |d| >= N - r are summed).  `work`: fourier_work_bytes() of device memory.  THE STREAM IS SYNCHRONISED once, after
+// the tables have been copied and before the kernels are enqueued.
+constexpr int kFourierRows = 8;          // outputs per thread along the summed axis' output index (rows in pass 1, columns in pass 2)
+constexpr int kFourierMaxSide = 16384;   // padded side: the tables stay below 2^15 entries, every index far inside int32
+size_t fourier_work_bytes(int H, int W, int pad);
+hipError_t launch_fourier(const void* src, double* dst, void* work, int H, int W, int64_t src_stride, int dtype, int pad, int boundary,
+                          const double* const taps[4], int ry, int rx, hipStream_t stream);
 // label_kernels.hip: connected components of the nonzero pixels (any ElemType; floats by their bits: NaN is set, -0.0 is not) numbered
 // as scipy.ndimage.label numbers them, into dst (dense H x W int32, 0 = background).  conn8: the full 3 x 3 structure, else the cross.
 // `parent`: H W int32 of device scratch, `counts`: label_count_words(H, W) more; the number of labels is left in the LAST word of

@@ -51,34 +51,6 @@ struct GaussArgs {
   GaussWeights wy, wx;
 };
 
-enum GaussExtend : int { kGaussReflect = 0, kGaussMirror, kGaussNearest, kGaussWrap, kGaussConstant };
-
-// index of position p in a line of length n under `mode`; -1: outside, the value is cval (constant mode).  n < 2^30, |p| < 2^31 - 2^30.
-__device__ __forceinline__ int gauss_fold(int p, int n, int mode) {
-  if ((unsigned)p < (unsigned)n) return p;
-  switch (mode) {
-    case kGaussNearest: return p < 0 ? 0 : n - 1;
-    case kGaussWrap: {
-      const int q = p % n;
-      return q < 0 ? q + n : q;
-    }
-    case kGaussReflect: {
-      const int period = 2 * n;
-      int q = p % period;
-      if (q < 0) q += period;
-      return q >= n ? period - 1 - q : q;
-    }
-    case kGaussMirror: {
-      if (n == 1) return 0;
-      const int period = 2 * n - 2;
-      int q = p % period;
-      if (q < 0) q += period;
-      return q >= n ? period - q : q;
-    }
-    default: return -1;
-  }
-}
-
 // scipy's store of a double into the output array: a C cast
 template <typename T>
 __device__ __forceinline__ T gauss_cast(double v) {

@@ -7,10 +7,14 @@
 * :func:`get_tilted_profile`, :func:`_calc_index_range`   reference ``linepattern.py:452-567``: same names, arguments, checks and
   error texts; the cubic-spline sampling runs through :func:`discorpy_amd.post.postprocessing.remap_coordinates`
 
-Out of scope: ``normalization_fft`` (needs an FFT), the 1-D peak search (``get_local_extrema_points``, ``select_good_peaks``:
-host-side scipy fitting on one profile at a time), the Radon functions (scikit-image) and therefore ``get_cross_points_hor_lines`` /
-``get_cross_points_ver_lines`` as whole functions: a caller runs their image-sized steps here and the per-profile steps with the
-reference.
+The ``norm=True`` step of ``get_cross_points_hor_lines`` / ``get_cross_points_ver_lines`` (``linepattern.py:657,737``),
+``normalization_fft``, is :func:`discorpy_amd.prep.preprocessing.normalization_fft`: with it every image-sized step of those two
+functions runs on the GPU.
+
+Out of scope: the 1-D peak search (``get_local_extrema_points``, ``select_good_peaks``: host-side scipy fitting on one profile at a
+time), the Radon functions (scikit-image) and therefore ``get_cross_points_hor_lines`` / ``get_cross_points_ver_lines`` as whole
+functions: what remains host-side of them is the slope search where no angle is given and, per profile, the peak search and its
+fits; a caller runs the image-sized steps here and those per-profile steps with the reference.
 
 The Gaussian runs as hand-written HIP kernels through ``dcp_correlate_sym_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/gauss_kernels.hip``) with scipy's arithmetic restated operation by operation (``DESIGN.md``), so the result equals scipy's bit

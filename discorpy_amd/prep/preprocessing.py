@@ -3,6 +3,8 @@
 * :func:`normalization`   reference ``discorpy/prep/preprocessing.py:50-73``: same name, arguments and default
 * :func:`median_filter`   the ``scipy.ndimage.median_filter(mat, size, mode="reflect")`` both :func:`normalization` (size 51) and the
   denoise step of the reference's ``binarization`` (size 2) rest on
+* :func:`normalization_fft`, :func:`_apply_fft_filter`, :func:`_make_window`   reference ``preprocessing.py:76-158``: same names, arguments
+  and defaults; the Fourier Gaussian filter runs on the GPU without an FFT (below)
 * :func:`label`, :func:`sum_labels`, :func:`center_of_mass`, :func:`find_objects`, :func:`binary_fill_holes`   the ``scipy.ndimage``
   functions of those names the reference calls on binary dot images (``preprocessing.py:247-445``, ``:966-997``), equal to scipy's
   results element for element
@@ -41,6 +43,19 @@ reference: the contrast is inverted iff ``2 * count > height * width`` on the ex
 promotion: a Python float against a float32 image is rounded to float32, a NumPy float64 scalar promotes the comparison to float64), so
 64-bit integer images beyond 2**53 are compared after rounding to double, as NumPy compares them with a float threshold.
 
+The Fourier Gaussian filter (``dcp_fourier_gauss_2d``, ``csrc/fourier_kernels.hip``): the reference pads the image, multiplies by the sign
+plane ``(-1)^(x + y)``, transforms, multiplies by a centred Gaussian window, transforms back, multiplies by the sign plane again, takes
+the real part and crops.  Sign and window are products of a factor per axis, so the whole operator is ``real(A_y m A_x^T)`` with one
+complex Toeplitz matrix per axis (:func:`_fourier_taps`; ``DESIGN.md``, "Fourier Gaussian filter"): two float64 passes that read the
+source through the pad's index fold and compute the cropped rows and columns only -- no padded plane, no complex plane of the padded
+size.  The tables are made here in NumPy (one 1-D inverse FFT of the window's factor per axis, cached) and the kernels sum the taps
+that matter: what is left out is bounded by 2**-56 of the table's absolute sum.  The result agrees with the reference's to rounding
+(both lie about 1e-15 of ``max|result|`` from a long-double evaluation), not bit for bit.  Departures, all raised before any device
+work: a ``sigma`` that is not a positive finite number and a ``pad`` that is not a non-negative integer raise ``ValueError`` (the
+reference silently produces NaNs for ``sigma = 0``); ``np.pad`` modes other than "reflect", "symmetric", "edge", "wrap" and "constant"
+(zeros) raise ``NotImplementedError``; complex and float16 input raise as for the median; a padded side above 16384 raises
+``NotImplementedError``.  The result is float64 for every input type, as the reference's is.
+
 Where the median differs from scipy:
 
 * floats are selected in IEEE 754 total order, so the result is defined bit for bit: ``-0.0`` sorts below ``+0.0`` (scipy treats them
@@ -56,6 +71,7 @@ Where the median differs from scipy:
 * only 2-D input is taken.
 """
 import ctypes
+import functools
 import operator
 
 import numpy as np
@@ -64,6 +80,8 @@ from .. import _ffi as F
 from ..post.postprocessing import _Image, _is_cai, _is_torch
 
 __all__ = ["normalization", "median_filter"]
+# the Fourier route to the same end (the names the reference's linepattern module calls, and the table behind them)
+FOURIER = ["normalization_fft", "_apply_fft_filter", "_make_window", "_fourier_taps"]
 # the dot-pattern route (labelling, measurements, hole filling and the reference's functions on top of them)
 # the binarization of a dot image in front of that route
 BINARIZATION = ["threshold_otsu", "clear_border", "opening", "binarization"]
@@ -182,6 +200,188 @@ def normalization(mat, size=51):
         rtype = mat.dtype if mat.is_floating_point() else torch.float64
         mean_val = mat_bck.to(torch.float64).mean().to(rtype)
         return mean_val * mat.to(rtype) / mat_bck.to(rtype)
+    mean_val = np.mean(mat_bck)
+    try:
+        mat_cor = mean_val * mat / mat_bck
+    except ZeroDivisionError:
+        mat_bck[mat_bck == 0.0] = mean_val
+        mat_cor = mean_val * mat / mat_bck
+    return mat_cor
+
+
+# --------------------------------------------------------------------------- the Fourier Gaussian background filter
+
+# np.pad's modes that fold an index (or pad with zeros), and the DCP_MODE_* each one is under dcp_fourier_gauss_2d
+_PAD_MODES = {"reflect": 5, "symmetric": 0, "edge": 4, "wrap": 7, "constant": 2}
+_FOURIER_MAX_SIDE = 16384       # kFourierMaxSide of csrc/dcp_internal.h: refused here before a table of that length is made
+
+
+def _make_window(height, width, sigma=10):
+    """
+    Create a 2D Gaussian window (reference ``preprocessing.py:76-99``): ``exp(-(x * x / num + y * y / num))`` with ``num = 2.0 * sigma *
+    sigma``, ``x = -(width - 1) / 2 ... (width - 1) / 2`` along the columns and ``y`` likewise along the rows.
+
+    Parameters
+    ----------
+    height : int
+        Height of the window.
+    width : int
+        Width of the window.
+    sigma : int
+        Sigma of the Gaussian window.
+
+    Returns
+    -------
+    array_like
+        2D float64 array.
+    """
+    xcenter = (width - 1.0) / 2.0
+    ycenter = (height - 1.0) / 2.0
+    y, x = np.ogrid[-ycenter:height - ycenter, -xcenter:width - xcenter]
+    num = 2.0 * sigma * sigma
+    window = np.exp(-(x * x / num + y * y / num))
+    return window
+
+
+def _taps_below_the_bound(n, sigma, total):
+    """
+    Mask of the ``d`` in ``0 .. n - 1`` at which ``c = ifft(w)`` is PROVABLY below ``2**-58 * total / n`` in magnitude (``total`` the sum
+    of ``|c|``), so that all of them together weigh less than ``2**-58`` of the table.  A float64 FFT leaves rounding noise of about
+    ``1e-17 max|c|`` in every entry, also where the true value is ``1e-40``; hundreds of such entries add up to more than the kernels'
+    truncation bound (``2**-56`` of the table) allows to drop, and the sums would run over the whole axis for nothing.  The bound:
+    ``w`` is the Gaussian ``g(x) = exp(-x^2 / (2 sigma^2))`` sampled at ``x = u - (n - 1) / 2``, ``u = 0 .. n - 1``.  Summed over ALL
+    integers ``u`` the transform is, by Poisson's formula, ``sigma sqrt(2 pi) / n`` times a sum over the integers ``m`` of
+    ``exp(-2 pi^2 sigma^2 (m - d / n)^2)`` up to phases; the samples outside ``0 .. n - 1`` add at most
+    ``(2 / n) g(a) (1 + sigma^2 / a)``, ``a = (n + 1) / 2`` (the first one left out plus the integral of the tail).  A window that is
+    cut off visibly at the ends of the axis (``sigma`` above about ``n / 18``) keeps every tap: its transform has an algebraic tail.
+    """
+    frac = np.arange(n, dtype=np.float64) / n
+    q = 2.0 * np.pi * np.pi * sigma * sigma
+    edge = (n + 1.0) / 2.0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        aliases = np.exp(-q * frac * frac) + np.exp(-q * (1.0 - frac) * (1.0 - frac)) + 2.0 * np.exp(-q) / (1.0 - np.exp(-q))
+        bound = sigma * np.sqrt(2.0 * np.pi) / n * aliases + 2.0 / n * np.exp(-edge * edge / (2.0 * sigma * sigma)) * (1.0 + sigma * sigma / edge)
+        return bound <= np.ldexp(total, -58) / n
+
+
+@functools.lru_cache(maxsize=8)
+def _fourier_taps_of(n, sigma):
+    x = np.arange(n, dtype=np.float64) - (n - 1.0) / 2.0
+    num = 2.0 * sigma * sigma
+    c = np.fft.ifft(np.exp(-(x * x / num)))
+    c[_taps_below_the_bound(n, sigma, np.abs(c).sum())] = 0.0
+    delta = np.arange(-(n - 1), n)
+    a = np.where(delta % 2 == 0, 1.0, -1.0) * c[delta % n]
+    re, im = np.ascontiguousarray(a.real), np.ascontiguousarray(a.imag)
+    re.setflags(write=False)
+    im.setflags(write=False)
+    return re, im
+
+
+def _fourier_taps(n, sigma):
+    """
+    The taps of the Fourier Gaussian filter along an axis of padded length ``n``: the operator ``S F^-1 diag(w) F S`` (``S`` the sign
+    ``(-1)^k``, ``F`` the DFT, ``w[k] = exp(-(k - (n - 1) / 2)^2 / (2 sigma^2))``) is the Toeplitz matrix ``A[j, k] = a(j - k)`` with
+    ``a(d) = (-1)^d c[d mod n]``, ``c = ifft(w)``; for odd ``n`` the wrapped half enters with the opposite sign,
+    ``a(d - n) = -a(d)``, which is why the table runs over the signed difference.
+
+    Returns
+    -------
+    (re, im) : two read-only float64 arrays of length ``2 n - 1``; index ``d + n - 1`` holds ``a(d)``.  Cached per ``(n, sigma)``.
+    ``c`` comes from a float64 inverse FFT; its entries that are provably negligible (:func:`_taps_below_the_bound`) are exact zeros
+    instead of the FFT's rounding noise, so that the kernels' support bound can see where the taps end.
+    """
+    return _fourier_taps_of(int(n), float(sigma))
+
+
+def _check_fft_arguments(mat, sigma, pad, mode):
+    """(sigma as a float, pad as an int, the DCP_MODE_* of ``mode``), or the documented exception; no device work."""
+    try:
+        sigma_f = float(sigma)
+    except (TypeError, ValueError):
+        sigma_f = float("nan")
+    if not (np.isfinite(sigma_f) and sigma_f > 0.0):
+        raise ValueError("sigma must be a positive finite number (got %r)" % (sigma,))
+    try:
+        pad_i = operator.index(pad)
+    except TypeError:
+        pad_i = -1
+    if pad_i < 0:
+        raise ValueError("pad must be a non-negative integer (got %r)" % (pad,))
+    if mode not in _PAD_MODES:
+        raise NotImplementedError("pad mode %r is not implemented on the GPU path (supported: %s)" % (mode, ", ".join(_PAD_MODES)))
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    return sigma_f, pad_i, _PAD_MODES[mode]
+
+
+def _apply_fft_filter(mat, sigma, pad, mode='reflect'):
+    """
+    Apply a Fourier Gaussian filter (reference ``preprocessing.py:102-128``) on the GPU, without an FFT: the reference's
+    ``real(ifft2(fft2(mat * sign) * window) * sign)`` on the padded image is ``real(A_y mat A_x^T)`` with the Toeplitz matrices of
+    :func:`_fourier_taps`, evaluated in float64 by ``dcp_fourier_gauss_2d`` for the cropped rows and columns only.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array (NumPy array, ROCm torch tensor or ``__cuda_array_interface__`` device array) of float32 / float64, an 8- to
+        64-bit integer type or bool.  A view whose rows are strided (``a[:, 3:-7]``) is read in place.
+    sigma : float
+        Sigma of the Gaussian filter.
+    pad : int
+        Pad width; it may exceed the image's sides.
+    mode : {"reflect", "symmetric", "edge", "wrap", "constant"}
+        ``np.pad``'s mode (``"constant"`` pads with zeros).
+
+    Returns
+    -------
+    array_like
+        2D float64 array of the input's kind and shape. Filtered image.
+    """
+    sigma, pad, code = _check_fft_arguments(mat, sigma, pad, mode)
+    img = _rows_image(mat)
+    height, width = img.shape
+    res, rptr = _new_like(img, (height, width), np.float64)
+    if height == 0 or width == 0:
+        return res
+    if max(height, width) + 2 * pad > _FOURIER_MAX_SIDE:
+        raise NotImplementedError("padded side above %d (got %d x %d)" % (_FOURIER_MAX_SIDE, height + 2 * pad, width + 2 * pad))
+    F.require_device()
+    taps = _fourier_taps(height + 2 * pad, sigma) + _fourier_taps(width + 2 * pad, sigma)
+    F.check(F.lib().dcp_fourier_gauss_2d(img.ptr, rptr, height, width, _row_stride(img), img.code, pad, code,
+                                         *[t.ctypes.data_as(F.C.POINTER(F.C.c_double)) for t in taps], img.mem, img.device, img.stream))
+    return res
+
+
+def normalization_fft(mat, sigma=10, pad=100, mode='reflect'):
+    """
+    Correct a non-uniform background image using a Fourier Gaussian filter (reference ``preprocessing.py:131-158``).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array (or anything ``numpy.asarray`` takes), or a torch tensor on a ROCm device.
+    sigma : int
+        Sigma of the Gaussian.
+    pad : int
+        Pad width.
+    mode : str
+        Padding mode: "reflect", "symmetric", "edge", "wrap" or "constant".
+
+    Returns
+    -------
+    array_like
+        2D float64 array. Corrected background image.  NumPy input: the background plane comes from the GPU (:func:`_apply_fft_filter`)
+        and the mean and the quotient are computed in NumPy as the reference writes them.  A device tensor: the plane is computed on
+        torch's current stream, its mean is taken in float64 and the quotient is formed with torch; a float64 tensor is returned.
+    """
+    _check_fft_arguments(mat, sigma, pad, mode)
+    mat, kind = _as_kind(mat, "normalization_fft takes NumPy arrays and torch tensors; use _apply_fft_filter for other device arrays")
+    mat_bck = _apply_fft_filter(mat, sigma, pad, mode=mode)
+    if kind == "torch":
+        import torch
+        mean_val = mat_bck.mean()
+        return mean_val * mat.to(torch.float64) / mat_bck
     mean_val = np.mean(mat_bck)
     try:
         mat_cor = mean_val * mat / mat_bck

@@ -499,6 +499,38 @@ int dcp_correlate_sym_2d(const void* src, void* dst, int height, int width, long
                          const double* weights_y, int radius_y, const double* weights_x, int radius_x,
                          int mode, double cval, int mem_kind, int device, void* stream);
 
+/* ---- line patterns: the Fourier Gaussian background filter ----
+ * discorpy/prep/preprocessing.py:76-158 (_apply_fft_filter behind normalization_fft): on the image padded by `pad` on every side
+ * (np.pad, sides Ny x Nx) the reference computes real(ifft2(fft2(m s) win) s) with s = (-1)^(x + y) and win a Gaussian centred on
+ * ((Ny - 1) / 2, (Nx - 1) / 2), and crops the pad again.  s and win are products of a factor per axis, so the operator is
+ * real(A_y m A_x^T) with one complex Toeplitz matrix per axis, A[j, k] = a(j - k); the call evaluates exactly that, without an FFT:
+ *     P[j, x]  = sum_k a_y(j - k) m[k, x]                                   (cropped rows j, every padded column x; complex)
+ *     dst[j, i] = sum_x a_x,re(i - x) P_re[j, x] - a_x,im(i - x) P_im[j, x]   (cropped columns i)
+ * in float64 with fused multiply-adds, m read from src through the pad's index fold (no padded plane exists).
+ *   taps_*   HOST pointers, per axis 2 N - 1 doubles each for the real and the imaginary part, N = side + 2 pad: entry d + N - 1 holds
+ *            a(d), d = -(N - 1) .. N - 1, with a(d) = (-1)^d c[d mod N] and c the inverse DFT of the window's factor along the axis.
+ *            The sums run over the taps with |d| <= R or |d| >= N - R only, R the smallest radius at which the taps left out sum to at
+ *            most 2^-56 of the table's sum of |re| + |im| (an eighth of float64's unit roundoff on the result's scale); a narrow
+ *            window keeps every tap.  The tables are read before the call returns.
+ *   pad_mode np.pad's mode as a DCP_MODE_*, a position p of a line of length n folded as dcp_correlate_sym_2d folds it:
+ *            DCP_MODE_MIRROR = "reflect" (period 2 n - 2; n = 1: index 0), DCP_MODE_REFLECT = "symmetric" (period 2 n),
+ *            DCP_MODE_NEAREST = "edge", DCP_MODE_WRAP = "wrap" (p mod n), DCP_MODE_CONSTANT = "constant" with value 0; any number of
+ *            folds (the pad may exceed the side).  The other DCP_MODE_* codes are refused.
+ *   src      rows `src_row_stride` elements apart (>= width), unit column stride, any DCP_DTYPE_*, each element converted to double as
+ *            NumPy converts it;  dst  dense (height, width) FLOAT64 whatever `dtype` is, not overlapping src
+ *   mem_kind DCP_MEM_HOST (staged up and down by the library) or DCP_MEM_DEVICE (enqueued on `stream`)
+ * A null table, pad < 0, an unknown pad_mode, a tap that is not finite and the refusals of every plane call are DCP_ERR_INVALID_ARG,
+ * a padded side above 16384 is DCP_ERR_UNSUPPORTED, all before any device call.  The planes of P (2 * height * (width + 2 pad) doubles)
+ * and the tables' device copies live in the library's scratch (dcp_release_scratch frees it).  The tables are copied to the device on
+ * `stream` and THE CALL WAITS FOR THAT COPY (so for the work enqueued on `stream` before it) before it enqueues its two kernels: it cannot be captured
+ * into a graph.  Kernels: fourier_rows_kernel<T> then fourier_cols_kernel (csrc/fourier_kernels.hip); dcp_debug_last_kernel() names
+ * them with the number of taps kept per axis. */
+int dcp_fourier_gauss_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype,
+                         int pad, int pad_mode,
+                         const double* taps_y_re, const double* taps_y_im,   /* 2 * (height + 2 * pad) - 1 each */
+                         const double* taps_x_re, const double* taps_x_im,   /* 2 * (width + 2 * pad) - 1 each */
+                         int mem_kind, int device, void* stream);
+
 /* ---- dot patterns: connected components, their measurements, hole filling ----
  * discorpy/prep/preprocessing.py:247-445 and :966-997 (scipy.ndimage.label, sum, center_of_mass, find_objects, binary_fill_holes).
  *

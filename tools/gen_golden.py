@@ -768,4 +768,93 @@ def g25():
 
 
 g25()
+
+
+# G26: the Fourier Gaussian filter, discorpy.prep.preprocessing._apply_fft_filter and normalization_fft (preprocessing.py:76-158), on the
+# cases of tests/test_fourier_gauss_gpu.py.  The module imports scikit-image at its top and never calls it in these two functions:
+# empty stand-in modules carry the names, as fake_h5py stands in for h5py in G20.  Per case: the input, sigma / pad / mode, the
+# reference's background plane and normalized result, and e_ref = max|reference - truth| / max|truth| with `truth` the same formula
+# evaluated through dense long-double DFT matrices (the reference's own rounding error: the tolerance of the tests is a multiple of it).
+# Images are uniform(50, 250) so that the background stays far from 0; integer types draw integers of that range (int8: up to 127),
+# bool draws coin flips.  Arrays only.
+def g26_cases():
+    rng = np.random.default_rng(2626)
+
+    def image(shape, dtype="float32"):
+        dt = np.dtype(dtype)
+        if dt == np.bool_:
+            return rng.random(shape) < 0.5
+        if dt.kind in "iu":
+            return rng.integers(50, min(250, np.iinfo(dt).max), shape, endpoint=True).astype(dt)
+        return rng.uniform(50.0, 250.0, shape).astype(dt)
+    cases = []
+    for shape in ((37, 52), (40, 51)):                                   # odd and even padded sides, the defaults and the cross-point sigma
+        for sigma in (10, 5):
+            cases.append(("s%dx%d_p100_s%d" % (shape + (sigma,)), image(shape), sigma, 100, "reflect"))
+    cases.append(("full_50x61", image((50, 61)), 1, 20, "symmetric"))     # every tap kept
+    cases.append(("full_30x45", image((30, 45)), 0.5, 10, "wrap"))
+    cases.append(("narrow_64x48", image((64, 48)), 40, 100, "reflect"))   # support far narrower than the side
+    cases.append(("pad0_33x47", image((33, 47)), 10, 0, "reflect"))
+    for mode in ("reflect", "symmetric", "edge", "wrap", "constant"):     # the pad beyond the side: several folds
+        cases.append(("folds_8x5_" + mode, image((8, 5)), 2, 23, mode))
+    for shape in ((1, 9), (9, 1), (2, 2)):
+        for mode in ("reflect", "symmetric"):
+            cases.append(("tiny_%dx%d_%s" % (shape + (mode,)), image(shape), 2, 4, mode))
+    for dt in ("float32", "float64", "int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64", "bool"):
+        cases.append(("type_" + dt, image((40, 51), dt), 3, 9, "reflect"))
+    cases.append(("view_40x58", image((40, 58)), 3, 9, "reflect"))       # filtered as the view a[:, 3:-7]
+    return cases
+
+
+def g26_truth(mat, sigma, pad, mode):
+    ld = np.longdouble
+    m = np.pad(mat, ((pad, pad), (pad, pad)), mode=mode).astype(ld)
+    pi = 4 * np.arctan(ld(1))
+
+    def operator_of(n):                                                   # S conj(F) / n diag(w) F S as real and imaginary parts
+        k = np.arange(n)
+        ph = (np.outer(k, k) % n).astype(ld) * 2 * pi / n
+        fr, fi = np.cos(ph), -np.sin(ph)
+        w = np.exp(-((k.astype(ld) - (n - 1) / ld(2)) ** 2) / (2 * ld(sigma) * ld(sigma)))
+        sg = np.where(k % 2 == 0, ld(1), ld(-1))
+        br, bi = (fr * w) @ fr + (fi * w) @ fi, (fr * w) @ fi - (fi * w) @ fr
+        return sg[:, None] * br * sg[None, :] / n, sg[:, None] * bi * sg[None, :] / n
+    (yr, yi), (xr, xi) = operator_of(m.shape[0]), operator_of(m.shape[1])
+    out = (yr @ m) @ xr.T - (yi @ m) @ xi.T
+    return out[pad:m.shape[0] - pad, pad:m.shape[1] - pad]
+
+
+def g26():
+    import types
+    import warnings
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    sys.modules["skimage.filters"].threshold_otsu = None
+    sys.modules["skimage.segmentation"].clear_border = None
+    sys.modules["skimage.transform"].radon = None
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import discorpy.prep.preprocessing as rprep
+    out = dict(names=[], sigma=[], pad=[], mode=[], e_ref=[])
+    for name, mat, sigma, pad, mode in g26_cases():
+        arg = mat[:, 3:-7] if name.startswith("view_") else mat
+        bck = rprep._apply_fft_filter(arg, sigma, pad, mode)
+        norm = rprep.normalization_fft(arg, sigma, pad, mode)
+        truth = g26_truth(arg, sigma, pad, mode)
+        assert bck.dtype == np.float64 and norm.dtype == np.float64 and bck.shape == arg.shape == norm.shape, name
+        e_ref = float(np.abs(bck - truth).max() / np.abs(truth).max())
+        assert 1e-17 < e_ref < 1e-14 and bck.min() > 0.05, (name, e_ref, bck.min())
+        out["names"].append(name)
+        out["sigma"].append(float(sigma))
+        out["pad"].append(pad)
+        out["mode"].append(mode)
+        out["e_ref"].append(e_ref)
+        out[name + "_in"], out[name + "_bck"], out[name + "_norm"] = mat, bck, norm
+    for k in ("names", "mode"):
+        out[k] = np.array(out[k])
+    out["sigma"], out["pad"], out["e_ref"] = f64(out["sigma"]), np.array(out["pad"], np.int64), f64(out["e_ref"])
+    save("g26_fourier_gauss", **out)
+
+
+g26()
 print("done")

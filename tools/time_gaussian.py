@@ -13,9 +13,24 @@ case, and there the line also carries the ratio scipy / GPU and whether scipy's 
 clock and package power under the 4096^2 float32 sigma-3 call.
 
     python tools/time_gaussian.py [--sides 2048,4096] [--dtypes float32,uint16] [--sigmas 3,10] [--rounds 5] [--reps 10] [--no-scipy]
+
+--fourier: the other Gaussian of the line-pattern route, with options of its own.  Time the Fourier Gaussian filter (prep.preprocessing._apply_fft_filter, dcp_fourier_gauss_2d: two Toeplitz passes in float64, no FFT) on
+device-resident float32 images against the same formula through an FFT library on the same device tensor
+(torch.nn.functional.pad, torch.fft.fft2 / ifft2 in complex128, the sign plane and the window made once outside the timed calls), the
+two routes alternated in one process, and once per case against the reference's route on the host (scipy.fftpack, restated).
+Cases: 2000 x 2000 at (sigma, pad) = (10, 100) and (5, 100), 4096 x 4096 at (10, 100), mode "reflect".
+
+Per case: warm-up calls of both routes, then `--rounds` (at least five) rounds; a round times `--reps` back-to-back calls of the
+Toeplitz route between device events, then the same of the FFT route.  Printed in ms per call: the median round of each route with
+its range, the ratio FFT / Toeplitz, the largest difference between the two outputs over max|output|, the taps the kernels kept per
+axis, the fused multiply-adds that makes and the rate it amounts to; with scipy the host's time, its ratio to the Toeplitz route and
+the difference of the outputs.  There is no threshold: the numbers go to DESIGN.md as they are.
+
+    python tools/time_gaussian.py --fourier [--cases 2000:10:100,2000:5:100,4096:10:100] [--rounds 5] [--reps 10] [--no-scipy]
 """
 import argparse
 import os
+import re
 import sys
 import time
 
@@ -27,6 +42,8 @@ MODE_NEAREST = 4        # DCP_MODE_NEAREST
 
 
 def main():
+    if "--fourier" in sys.argv[1:]:
+        return fourier_main([v for v in sys.argv[1:] if v != "--fourier"])
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
     ap.add_argument("--dtypes", default="float32,uint16")
@@ -112,6 +129,98 @@ def main():
                                                                              F.MEM_DEVICE, dev, None)),
                                       lambda: F.check(L.dcp_stream_synchronize(dev, None)))
         print("clock under the %d x %d float32 sigma-3 call: %s" % (side, side, clk), flush=True)
+
+
+def reference_filter(mat, sigma, pad, mode="reflect"):
+    """discorpy/prep/preprocessing.py:102-128 restated on scipy.fftpack."""
+    from scipy.fftpack import fft2, ifft2
+    mat = np.pad(mat, ((pad, pad), (pad, pad)), mode=mode)
+    (height, width) = mat.shape
+    xcenter, ycenter = (width - 1.0) / 2.0, (height - 1.0) / 2.0
+    y, x = np.ogrid[-ycenter:height - ycenter, -xcenter:width - xcenter]
+    num = 2.0 * sigma * sigma
+    window = np.exp(-(x * x / num + y * y / num))
+    x, y = np.meshgrid(np.arange(0, width), np.arange(0, height))
+    matsign = np.power(-1.0, x + y)
+    mat = np.real(ifft2(fft2(mat * matsign) * window) * matsign)
+    return mat[pad:height - pad, pad:width - pad]
+
+
+def fourier_main(argv):
+    ap = argparse.ArgumentParser(prog="time_gaussian.py --fourier", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cases", default="2000:10:100,2000:5:100,4096:10:100", help="side:sigma:pad, comma-separated")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--no-scipy", action="store_true")
+    a = ap.parse_args(argv)
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    import torch
+    from discorpy_amd import _ffi as F
+    from discorpy_amd.prep import preprocessing as prep
+    F.require_device()
+    rng = np.random.default_rng(11)
+    for spec in a.cases.split(","):
+        side, sigma, pad = spec.split(":")
+        side, sigma, pad = int(side), float(sigma), int(pad)
+        # a line-pattern-like image: a smooth illumination gradient under noise, far from 0
+        img = ((rng.random((side, side), dtype=np.float32) + np.linspace(0.5, 1.5, side, dtype=np.float32)) * 100.0).astype(np.float32)
+        t = torch.from_numpy(img).to("cuda:0")
+        n = side + 2 * pad
+        idx = torch.arange(n, device=t.device)
+        sign = torch.where((idx[:, None] + idx[None, :]) % 2 == 0, 1.0, -1.0).to(torch.float64)
+        window = torch.from_numpy(prep._make_window(n, n, sigma)).to(t.device)
+
+        def toeplitz():
+            return prep._apply_fft_filter(t, sigma, pad)
+
+        def library():
+            m = torch.nn.functional.pad(t[None, None].to(torch.float64), (pad, pad, pad, pad), mode="reflect")[0, 0]
+            out = torch.fft.ifft2(torch.fft.fft2(m * sign) * window).real * sign
+            return out[pad:n - pad, pad:n - pad]
+
+        routes = {"toeplitz": toeplitz, "fft": library}
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / a.reps
+        outs = {}
+        for name, fn in routes.items():
+            for _ in range(a.warmup):
+                outs[name] = fn()
+            if name == "toeplitz":
+                kernels = F.last_kernel()
+        torch.cuda.synchronize()
+        rounds = {name: [] for name in routes}
+        for _ in range(a.rounds):
+            for name, fn in routes.items():
+                rounds[name].append(timed(fn))
+        med = {name: float(np.median(v)) for name, v in rounds.items()}
+        got = {name: v.cpu().numpy() for name, v in outs.items()}
+        diff = np.abs(got["toeplitz"] - got["fft"]).max() / np.abs(got["fft"]).max()
+        taps = [int(v) for pair in re.findall(r"taps=(\d+) of (\d+)", kernels) for v in pair]
+        ky, kx = taps[0], taps[2]
+
+        def steps(kept, whole):          # indices a block of 8 outputs walks: its cyclic window of 2 R + 8, or the whole axis
+            return n if kept == whole else min(n, (kept - 1) // 2 + 8)
+        fma = 2.0 * side * n * steps(ky, taps[1]) + 2.0 * side * side * steps(kx, taps[3])     # per step and output: re and im
+        line = ("float32 %4d x %-4d sigma %-3g pad %-3d toeplitz %8.4f ms (rounds %.4f .. %.4f)  fft library %8.4f ms (rounds %.4f .. %.4f)"
+                "  fft / toeplitz %.2f  |difference| / max %.2e  taps %d, %d  %.3g FMA = %.2f TFLOP/s float64" % (
+                    side, side, sigma, pad, med["toeplitz"], min(rounds["toeplitz"]), max(rounds["toeplitz"]), med["fft"], min(rounds["fft"]),
+                    max(rounds["fft"]), med["fft"] / med["toeplitz"], diff, ky, kx, fma, 2.0 * fma / (med["toeplitz"] * 1e-3) / 1e12))
+        if not a.no_scipy:
+            t0 = time.perf_counter()
+            ref = reference_filter(img, sigma, pad)
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            line += "  scipy.fftpack on the host %9.1f ms  ratio %7.1f  |difference| / max %.2e" % (
+                cpu_ms, cpu_ms / med["toeplitz"], np.abs(got["toeplitz"] - ref).max() / np.abs(ref).max())
+        print(line + "  [%s]" % kernels, flush=True)
 
 
 if __name__ == "__main__":
