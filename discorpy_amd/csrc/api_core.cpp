@@ -758,8 +758,9 @@ int dcp_debug_bounds(uint64_t* out, int n, int reset) {
 #endif
   out[0] = out[1] = out[2] = out[3] = 0;
   DCP_HIP(hipDeviceSynchronize());
-  hipError_t (*readers[8])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_color, dcp::read_bounds_spline, dcp::read_bounds_spline_color,
-                                                          dcp::read_bounds_spline_frames, dcp::read_bounds_gauss, dcp::read_bounds_label, dcp::read_bounds_fourier};
+  hipError_t (*readers[9])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_color, dcp::read_bounds_spline, dcp::read_bounds_spline_color,
+                                                          dcp::read_bounds_spline_frames, dcp::read_bounds_gauss, dcp::read_bounds_label, dcp::read_bounds_fourier,
+                                                          dcp::read_bounds_profile};
   for (auto rd : readers) {
     unsigned long long v[4];
     DCP_HIP(rd(v, reset != 0));

@@ -1,0 +1,100 @@
+// api_profile.cpp -- dcp_local_extrema_rows, dcp_window_slope_rows and dcp_tilted_profiles_2d of the C ABI (include/discorpy_hip.h): plane
+// calls (api_plane.h) on a plane of profiles or on the image the profiles are taken from, their argument checks, the workspace of the
+// bands' coefficient planes (one lease of the spline workspace) and the launches of profile_kernels.hip.
+#include "api_plane.h"
+
+using namespace dcpapi;
+
+constexpr size_t kProfileWorkCap = (size_t)512 << 20;   // the bands' planes of one group; a single band wider than this still gets its own
+
+static int float_plane_only(int dtype) {
+  if (dtype != dcp::kF32 && dtype != dcp::kF64) return fail(DCP_ERR_UNSUPPORTED, "dtype %d: profiles are float32 or float64", dtype);
+  return DCP_OK;
+}
+
+extern "C" {
+
+int dcp_local_extrema_rows(const void* src, double* dst, int nrows, int length, long src_row_stride, int dtype, int radius, double sensitive,
+                           int subpixel, int mem_kind, int device, void* stream) {
+  PlaneCall c;
+  int rc;
+  if ((rc = make_plane_call(&c, src, dst, nrows, length, src_row_stride, dtype, sizeof(double), kPixelLimit, kReadsWindow, mem_kind, device, stream)) != DCP_OK)
+    return rc;
+  if ((rc = float_plane_only(dtype)) != DCP_OK) return rc;
+  if (radius < 0) return fail(DCP_ERR_INVALID_ARG, "radius must be at least 0 (got %d)", radius);
+  if (radius > dcp::kPeakMaxRadius) return fail(DCP_ERR_UNSUPPORTED, "radius above %d (got %d)", dcp::kPeakMaxRadius, radius);
+  if (subpixel != 0 && subpixel != 1) return fail(DCP_ERR_INVALID_ARG, "subpixel must be 0 or 1 (got %d)", subpixel);
+  if (subpixel && radius < 1) return fail(DCP_ERR_INVALID_ARG, "subpixel needs a radius of at least 1");
+  if (sensitive != sensitive) return fail(DCP_ERR_INVALID_ARG, "sensitive is NaN");
+  return run_plane(c, false, 0, [&](const void* s, void* d, int64_t rs, void*) {
+    return dcp::launch_peak_rows(s, static_cast<double*>(d), nrows, length, rs, dtype, radius, sensitive, subpixel != 0, c.stream);
+  });
+}
+
+int dcp_window_slope_rows(const void* src, void* dst, int nrows, int length, long src_row_stride, int dtype, int size, int mem_kind, int device,
+                          void* stream) {
+  PlaneCall c;
+  int rc;
+  if ((rc = make_plane_call(&c, src, dst, nrows, length, src_row_stride, dtype, kSameElem, kPixelLimit, kReadsWindow, mem_kind, device, stream)) != DCP_OK)
+    return rc;
+  if ((rc = float_plane_only(dtype)) != DCP_OK) return rc;
+  if (size < 3 || !(size & 1)) return fail(DCP_ERR_INVALID_ARG, "size must be odd and at least 3 (got %d)", size);
+  if (nrows > 65535) return fail(DCP_ERR_UNSUPPORTED, "more than 65535 rows (got %d)", nrows);
+  return run_plane(c, false, 0, [&](const void* s, void* d, int64_t rs, void*) {
+    return dcp::launch_window_slope(s, d, nrows, length, rs, dtype, size, c.stream);
+  });
+}
+
+int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, int direction, int nprofiles,
+                           int length, const double* ycoords, const double* xcoords, const int32_t* band_lo, const int32_t* band_count,
+                           int mem_kind, int device, void* stream) {
+  PlaneCall c;
+  int rc;
+  // (the destination is not a plane of the source's shape: checked here, and the round trip of host memory is this call's own)
+  if ((rc = make_plane_call(&c, src, nullptr, height, width, src_row_stride, dtype, 0, kSideLimit, kReadsWindow, mem_kind, device, stream)) != DCP_OK)
+    return rc;
+  if ((rc = float_plane_only(dtype)) != DCP_OK) return rc;
+  if (!dst || !ycoords || !xcoords || !band_lo || !band_count) return fail(DCP_ERR_INVALID_ARG, "null dst / coordinate / band pointer");
+  if (direction != 0 && direction != 1) return fail(DCP_ERR_INVALID_ARG, "direction must be 0 (bands of rows) or 1 (bands of columns), got %d", direction);
+  if (nprofiles < 1 || length < 1) return fail(DCP_ERR_INVALID_ARG, "nprofiles and length must be at least 1 (got %d, %d)", nprofiles, length);
+  if (nprofiles > 65535) return fail(DCP_ERR_UNSUPPORTED, "more than 65535 profiles (got %d)", nprofiles);
+  if ((int64_t)nprofiles * (int64_t)length > 2147483647LL) return fail(DCP_ERR_UNSUPPORTED, "nprofiles * length above 2^31 - 1");
+  const bool vertical = direction == 1;
+  const size_t table = dcp::kProfileGroupMax * 24;      // the band table in front of the planes (profile_kernels.hip)
+  size_t all = 0, widest = 0;
+  for (int p = 0; p < nprofiles; ++p) {
+    if (band_lo[p] < 0 || band_count[p] < 1 || (int64_t)band_lo[p] + band_count[p] > (vertical ? width : height))
+      return fail(DCP_ERR_INVALID_ARG, "band %d: [%d, %d + %d) leaves the image", p, band_lo[p], band_lo[p], band_count[p]);
+    const size_t bytes = dcp::profile_band_elems(height, width, vertical, band_count[p]) * sizeof(double);
+    all += bytes;
+    widest = bytes > widest ? bytes : widest;
+  }
+  const size_t work_bytes = table + (all <= kProfileWorkCap ? all : (widest > kProfileWorkCap ? widest : kProfileWorkCap));
+  const size_t out_bytes = (size_t)nprofiles * (size_t)length * c.esz, coord_bytes = (size_t)nprofiles * (size_t)length * sizeof(double);
+  {
+    const char *d0 = (const char*)dst, *d1 = d0 + out_bytes;
+    const char *s0 = (const char*)src, *s1 = s0 + ((size_t)(height - 1) * (size_t)src_row_stride + (size_t)width) * c.esz;
+    if (s0 < d1 && d0 < s1) return fail(DCP_ERR_INVALID_ARG, "src and dst overlap: %s", kReadsNeighbourhood);
+  }
+  PlaneDevice on(c.device);
+  if (on.rc != DCP_OK) return on.rc;
+  WorkspaceLease lease;
+  if ((rc = lease.acquire(work_bytes, c.stream)) != DCP_OK) return rc;
+  auto launch = [&](const void* s, void* d, int64_t rs, const void* yc, const void* xc) {
+    return dcp::launch_tilted_profiles(s, d, height, width, rs, dtype, vertical, nprofiles, length, static_cast<const double*>(yc),
+                                       static_cast<const double*>(xc), band_lo, band_count, lease.buf, work_bytes, c.stream);
+  };
+  if (!c.host) {
+    DCP_HIP(launch(c.src, dst, c.rs, ycoords, xcoords));
+    return DCP_OK;
+  }
+  HostTrip t = packed_rows(c);
+  t.y_up = ycoords;
+  t.x_up = xcoords;
+  t.plane = coord_bytes;
+  t.dst = dst;
+  t.out_bytes = out_bytes;
+  return host_round_trip(t, c.stream, [&](const void* dsrc, void* ddst, void* dy, void* dx) { return launch(dsrc, ddst, (int64_t)c.W, dy, dx); });
+}
+
+}  // extern "C"

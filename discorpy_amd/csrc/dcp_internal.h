@@ -202,6 +202,7 @@ hipError_t read_bounds_spline_frames(unsigned long long* out, bool reset);
 hipError_t read_bounds_gauss(unsigned long long* out, bool reset);
 hipError_t read_bounds_label(unsigned long long* out, bool reset);
 hipError_t read_bounds_fourier(unsigned long long* out, bool reset);
+hipError_t read_bounds_profile(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -296,6 +297,30 @@ constexpr int kFourierMaxSide = 16384;   // padded side: the tables stay below 2
 size_t fourier_work_bytes(int H, int W, int pad);
 hipError_t launch_fourier(const void* src, double* dst, void* work, int H, int W, int64_t src_stride, int dtype, int pad, int boundary,
                           const double* const taps[4], int ry, int rx, hipStream_t stream);
+// profile_kernels.hip: the per-profile steps of the line-pattern route on an (N, L) plane of float32 / float64 profiles (kF32, kF64), rows of
+// src `src_stride` elements apart, every dst dense.
+// The local minima of get_local_extrema_points: sample i of range(radius, L - radius - 1) is a point iff it equals the minimum of its window
+// [i - radius, i + radius], the window holds no NaN and |(v - m) / m| > sensitive (0 where m == 0), m = np.mean of the `radius` largest
+// window elements in ascending order (NumPy's pairwise sum, then one division), all in the row's type; the comparison with `sensitive`
+// is made in float64.  dst: (N, L) doubles; row r holds its positions in ascending order and, in element L - 1, their number.
+// subpixel: every position refined by the parabola through d[i - 1], d[i], d[i + 1] in float64 (needs radius >= 1).
+constexpr int kPeakMaxRadius = 128;            // the sorted tail stays inside one block of NumPy's pairwise sum
+hipError_t launch_peak_rows(const void* src, double* dst, int N, int L, int64_t src_stride, int dtype, int radius, double sensitive, bool subpixel,
+                            hipStream_t stream);
+// sliding_window_slope before its normalisation: |slope| of the least-squares line through the `size` (odd, >= 3) samples around every sample
+// of the edge-padded row; products and sum in float64 (k ascending), the quotient rounded to the row's type.  dst of src's type; N <= 65535
+hipError_t launch_window_slope(const void* src, void* dst, int N, int L, int64_t src_stride, int dtype, int size, hipStream_t stream);
+// `nprof` tilted profiles of `len` samples of the H x W plane at src: profile p is the cubic spline (scipy's prefilter and weights, mode
+// "nearest") of its own band -- rows (vertical: columns) band_lo[p] .. band_lo[p] + band_n[p] - 1 -- sampled at the image coordinates
+// (ycoord, xcoord)[p][i] (device doubles).  band_lo / band_n are HOST arrays.  dst: (nprof, len) of src's type.  `work`: work_bytes of
+// device memory: kProfileGroupMax * 24 bytes for the band table, then room for profile_band_elems() doubles of the widest band at least;
+// profiles whose planes do not fit together run in groups.
+// THE STREAM IS SYNCHRONISED once per group, after the group's band table has been copied.
+constexpr int kProfileGroupMax = 256;          // profiles per group: their band table travels in one copy
+size_t profile_band_elems(int H, int W, bool vertical, int n);
+hipError_t launch_tilted_profiles(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, bool vertical, int nprof, int len,
+                                  const double* ycoord, const double* xcoord, const int32_t* band_lo, const int32_t* band_n, void* work, size_t work_bytes,
+                                  hipStream_t stream);
 // label_kernels.hip: connected components of the nonzero pixels (any ElemType; floats by their bits: NaN is set, -0.0 is not) numbered
 // as scipy.ndimage.label numbers them, into dst (dense H x W int32, 0 = background).  conn8: the full 3 x 3 structure, else the cross.
 // `parent`: H W int32 of device scratch, `counts`: label_count_words(H, W) more; the number of labels is left in the LAST word of

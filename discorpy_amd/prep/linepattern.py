@@ -11,10 +11,27 @@ The ``norm=True`` step of ``get_cross_points_hor_lines`` / ``get_cross_points_ve
 ``normalization_fft``, is :func:`discorpy_amd.prep.preprocessing.normalization_fft`: with it every image-sized step of those two
 functions runs on the GPU.
 
-Out of scope: the 1-D peak search (``get_local_extrema_points``, ``select_good_peaks``: host-side scipy fitting on one profile at a
-time), the Radon functions (scikit-image) and therefore ``get_cross_points_hor_lines`` / ``get_cross_points_ver_lines`` as whole
-functions: what remains host-side of them is the slope search where no angle is given and, per profile, the peak search and its
-fits; a caller runs the image-sized steps here and those per-profile steps with the reference.
+* :func:`get_cross_points_hor_lines`, :func:`get_cross_points_ver_lines`   reference ``linepattern.py:604-761``: same names, arguments
+  and defaults; every step but the final scale and rotation of the positions runs on the GPU
+* :func:`get_tilted_profiles`   N calls of :func:`get_tilted_profile` on one image in one (``dcp_tilted_profiles_2d``)
+* :func:`sliding_window_slope`, :func:`get_local_extrema_points`, :func:`locate_subpixel_point`   reference ``linepattern.py:46-72,
+  155-274``: same names, arguments and defaults, on one profile or on an (N, L) batch of profiles (``dcp_window_slope_rows``,
+  ``dcp_local_extrema_rows``; the kernels are in ``csrc/profile_kernels.hip``)
+
+These names are listed in :data:`CROSS_POINTS`; ``__all__`` keeps the three names it had.
+
+Where the peak search differs from the reference: the sub-pixel position of a point is the closed form of the parabola through
+``d[i-1], d[i], d[i+1]`` (``a = (d0 - 2 d1 + d2) / 2``, ``b = (-3 d0 + 4 d1 - d2) / 2``, vertex ``-b / (2 a)``) instead of
+``np.polyfit``'s least-squares solve: the two agree to ~1e-13 pixel, except that on exactly collinear triples the polyfit's rounding
+noise can leave ``a`` nonzero where the closed form gives ``a == 0`` and falls back to the argmin; ``select_peaks=True`` (a
+``scipy.optimize.curve_fit`` per peak on the host) raises ``NotImplementedError``; a search radius above 128 raises
+``NotImplementedError``; element types other than float32 are searched as float64.  The integer positions are the reference's exactly:
+the minimum test, the mean of the ``radius`` largest window elements (NumPy's pairwise sum, restated bit for bit) and the sensitivity
+quotient are evaluated in the profile's own type as NumPy 2 evaluates them.
+
+Out of scope: the selection of good peaks behind the peak search (``select_good_peaks``: a scipy ``curve_fit`` per peak) and the Radon
+functions (``calc_slope_distance_hor_lines`` / ``calc_slope_distance_ver_lines``: scikit-image): a caller passes the slope and the
+distance to the cross-point functions, as the reference's signature has it.
 
 The Gaussian runs as hand-written HIP kernels through ``dcp_correlate_sym_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/gauss_kernels.hip``) with scipy's arithmetic restated operation by operation (``DESIGN.md``), so the result equals scipy's bit
@@ -33,9 +50,13 @@ import numpy as np
 
 from .. import _ffi as F
 from ..post.postprocessing import _Image, _MODES, remap_coordinates
-from .preprocessing import _as_kind, _is_complex, _row_stride, _rows_image
+from .preprocessing import _as_kind, _is_complex, _row_stride, _rows_image, _thres_double, normalization_fft
 
 __all__ = ["gaussian_filter", "convert_chessboard_to_linepattern", "get_tilted_profile"]
+# the cross-point route (batched profiles, the peak search and the reference's two functions on top of them)
+CROSS_POINTS = ["get_tilted_profiles", "sliding_window_slope", "locate_subpixel_point", "get_local_extrema_points",
+                "get_cross_points_hor_lines", "get_cross_points_ver_lines"]
+PEAK_MAX_RADIUS = 128          # dcp_local_extrema_rows: the sorted tail stays inside one block of NumPy's pairwise sum
 
 
 def _gaussian_weights(sigma, truncate=4.0, radius=None):
@@ -255,3 +276,406 @@ def get_tilted_profile(mat, index, angle_deg, direction):
         xmax = int(np.ceil(np.amax(xlist))) + 1
         profile = remap_coordinates(mat[:, xmin:xmax], ylist, xlist - xmin, order=3, mode="nearest")
     return xlist, ylist, profile
+
+
+# --------------------------------------------------------------------------- the cross-point route
+
+def _line_coordinates(height, width, index, angle, direction):
+    """(xlist, ylist, first row / column of the band, its count): the expressions of the reference's ``get_tilted_profile``."""
+    if direction == "horizontal":
+        rlist = np.linspace(0, np.floor(width / np.cos(angle)), width)
+        xlist = np.clip(rlist * np.cos(angle), 0, width - 1)
+        ylist = np.clip(index + rlist * np.sin(-angle), 0, height - 1)
+        across = ylist
+    else:
+        rlist = np.linspace(0, np.floor(height / np.cos(angle)), height)
+        ylist = np.clip(rlist * np.cos(angle), 0, height - 1)
+        xlist = np.clip(index + rlist * np.sin(angle), 0, width - 1)
+        across = xlist
+    lo = int(np.floor(np.amin(across)))
+    return xlist, ylist, lo, int(np.ceil(np.amax(across))) + 1 - lo
+
+
+def get_tilted_profiles(mat, indices, angle_deg, direction):
+    """
+    Get the intensity-profiles along N parallel tilted lines across an image: what N calls of :func:`get_tilted_profile` return,
+    from one call of the GPU.  Positive angle is counterclockwise.
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array: a NumPy array or a ROCm torch tensor.  float32 / float64 take the batched kernels (``dcp_tilted_profiles_2d``: the
+        cubic prefilter of every line's own band, then the samples); other element types go line by line through
+        :func:`get_tilted_profile`.
+    indices : sequence of float
+        Index of every line.
+    angle_deg : float
+        Tilted angle in Degree.
+    direction : {"horizontal", "vertical"}
+        Direction of the line-profiles.
+
+    Returns
+    -------
+    xlists : ndarray
+        (N, L) float64. x-positions of the points on every line, the reference's bit for bit.
+    ylists : ndarray
+        (N, L) float64. y-positions of the points on every line.
+    profiles : array_like
+        (N, L) of the input's kind and dtype. Intensities of the points on every line.
+    """
+    if direction not in ("horizontal", "vertical"):
+        raise ValueError("direction must be 'horizontal' or 'vertical'")
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    shape = tuple(mat.shape) if hasattr(mat, "shape") else np.shape(mat)
+    if len(shape) != 2:
+        raise ValueError("Input must be a 2D array !!!")
+    (height, width) = shape
+    (min_idx, max_idx) = _calc_index_range(height, width, angle_deg, direction)
+    angle = angle_deg * np.pi / 180.0
+    indices = np.atleast_1d(np.asarray(indices))
+    if indices.ndim != 1:
+        raise ValueError("indices must be a 1D sequence")
+    for index in indices:
+        if (index < min_idx) or (index > max_idx):
+            raise ValueError("Input index is out of possible range: [{0}, {1}]".format(min_idx, max_idx))
+    nprof, length = len(indices), width if direction == "horizontal" else height
+    xlists, ylists = np.empty((nprof, length)), np.empty((nprof, length))
+    band_lo, band_n = np.empty(nprof, np.int32), np.empty(nprof, np.int32)
+    for p, index in enumerate(indices):
+        xlists[p], ylists[p], band_lo[p], band_n[p] = _line_coordinates(height, width, index, angle, direction)
+    mat, kind = _as_kind(mat, "get_tilted_profiles takes NumPy arrays and torch tensors")
+    img = _Image(mat, 2)
+    if img.code not in (F.DTYPE_BY_NAME["float32"], F.DTYPE_BY_NAME["float64"]) or nprof == 0:
+        rows = [get_tilted_profile(mat, index, angle_deg, direction)[2] for index in indices]
+        if kind == "torch":
+            import torch
+            return xlists, ylists, torch.stack(rows) if rows else mat.new_empty((0, length))
+        return xlists, ylists, np.asarray(rows, dtype=img.dtype).reshape(nprof, length)
+    img = _rows_image(img)
+    res, optr = img.empty((nprof, length))
+    F.require_device()
+    if kind == "torch":
+        import torch
+        ydev, xdev = torch.from_numpy(ylists).to(mat.device), torch.from_numpy(xlists).to(mat.device)
+        yptr, xptr = ydev.data_ptr(), xdev.data_ptr()
+    else:
+        yptr, xptr = ylists.ctypes.data, xlists.ctypes.data
+    i32p = F.C.POINTER(F.C.c_int32)
+    F.check(F.lib().dcp_tilted_profiles_2d(img.ptr, optr, height, width, _row_stride(img), img.code, 0 if direction == "horizontal" else 1, nprof,
+                                           length, yptr, xptr, band_lo.ctypes.data_as(i32p), band_n.ctypes.data_as(i32p), img.mem, img.device,
+                                           img.stream))
+    return xlists, ylists, res
+
+
+def _profile_rows(list_data, what):
+    """(``list_data`` as a fresh (N, L) float32 / float64 NumPy array, whether it was one 1-D profile)."""
+    if _is_complex(list_data):
+        raise TypeError("Complex type not supported")
+    rows, _ = _as_kind(list_data, "%s takes NumPy arrays and torch tensors" % what)
+    if hasattr(rows, "detach"):
+        rows = rows.detach().cpu().numpy()
+    rows = np.array(rows, dtype=None if rows.dtype in (np.float32, np.float64) else np.float64)
+    if rows.ndim not in (1, 2):
+        raise ValueError("%s takes a 1D array or an (N, L) batch of them" % what)
+    return np.atleast_2d(rows), rows.ndim == 1
+
+
+def sliding_window_slope(list_data, size=3, norm=True):
+    """
+    Compute the absolute slopes of a linear fit within a sliding window across the input data, normalized by the mean slope if norm
+    is True (reference ``linepattern.py:155-192``).
+
+    Parameters
+    ----------
+    list_data : array-like
+        1d-array, or an (N, L) batch of them.  float32 / float64; other types are read as float64.
+    size : int, optional
+        Size of the sliding window for the linear fit.
+    norm : bool, optional
+        Normalize the result by the mean slope if True.
+
+    Returns
+    -------
+    array_like
+        Normalized absolute slopes for each data point, of the input's shape.  The slope of the window's least-squares line is the
+        closed form ``sum_k (k - r) p[i + k] / sum_k (k - r)^2`` of the reference's ``np.polyfit`` (``dcp_window_slope_rows``; float64
+        sums, agreeing with the polyfit to ~1e-14 of the largest slope); the division by the mean is NumPy's, row by row.
+    """
+    rows, single = _profile_rows(list_data, "sliding_window_slope")
+    npoint = rows.shape[1]
+    if npoint < 3:
+        raise ValueError("Data size must be larger than 2")
+    size = int(np.clip(size, 3, npoint))
+    if size % 2 == 0:
+        size += 1
+    slopes = np.empty_like(rows)
+    if rows.shape[0] > 0:
+        F.require_device()
+        img = _rows_image(rows)
+        F.check(F.lib().dcp_window_slope_rows(img.ptr, slopes.ctypes.data, rows.shape[0], npoint, _row_stride(img), img.code, size, img.mem, img.device,
+                                              img.stream))
+    if norm is True:
+        for p in range(rows.shape[0]):
+            nmean = np.mean(slopes[p])
+            if nmean != 0.0:
+                slopes[p] = slopes[p] / nmean
+    return slopes[0] if single else slopes
+
+
+def locate_subpixel_point(list_point, option="min"):
+    """
+    Locate the extremum point of a 1D array with subpixel accuracy (reference ``linepattern.py:46-72``).
+
+    Parameters
+    ----------
+    list_point : array_like
+        1D array.
+    option : {"min", "max"}
+        To locate the minimum point or the maximum point.
+
+    Returns
+    -------
+    float
+        Subpixel position of the extremum point.  Three points: the vertex of the parabola through them in closed form (what the
+        reference's ``np.polyfit`` solves by least squares; module docstring); any other number of points: ``np.polyfit``.
+    """
+    num_point = len(list_point)
+    if num_point == 3:
+        d0, d1, d2 = (np.float64(v) for v in list_point)
+        a = (d0 - 2.0 * d1 + d2) / 2.0
+        b = (-3.0 * d0 + 4.0 * d1 - d2) / 2.0
+    else:
+        a, b, _ = np.polyfit(np.arange(num_point), list_point, 2)
+    if option == "min":
+        pos = np.argmin(list_point)
+    else:
+        pos = np.argmax(list_point)
+    if a != 0.0:
+        with np.errstate(all="ignore"):
+            num = - b / (2 * a)
+        if (num >= 0) and (num < num_point):
+            pos = num
+    return pos
+
+
+def _normalize_background(list_data):
+    """The ``norm`` step of the reference's ``get_local_extrema_points`` (``linepattern.py:236-253``) on one row, call for call."""
+    num_point = len(list_data)
+    xlist = np.arange(num_point)
+    mat_comb = np.asarray(np.vstack((xlist, list_data)))
+    mat_sort = mat_comb[:, mat_comb[1, :].argsort()]
+    list_sort = mat_sort[1]
+    ndrop = int(0.25 * num_point)
+    (a1, a0) = np.polyfit(xlist[ndrop:-ndrop - 1], list_sort[ndrop:-ndrop - 1], 1)[:2]
+    list_fit = a1 * xlist + a0
+    l_thres, u_thres = a0, a1 * xlist[-1] + a0
+    list_sort[(list_fit >= l_thres) & (list_fit <= u_thres)] = list_fit[(list_fit >= l_thres) & (list_fit <= u_thres)]
+    mat_sort[1] = list_sort
+    nmean = np.mean(np.abs(list_fit))
+    backgr = mat_sort[:, mat_sort[0, :].argsort()][1]
+    return np.divide(list_data, backgr, out=nmean * np.ones_like(list_data), where=backgr != 0)
+
+
+def get_local_extrema_points(list_data, option="min", radius=7, sensitive=0.1, denoise=True, norm=True, subpixel=True, select_peaks=False,
+                             **kwargs):
+    """
+    Get a list of local extremum points from a 1D array (reference ``linepattern.py:195-274``), or from every row of a batch.
+
+    Parameters
+    ----------
+    list_data : array_like
+        1D array, or an (N, L) batch of them.  float32 / float64; other types are read as float64.
+    option : {"min", "max"}
+        To get minimum points or maximum points
+    radius : int
+        Search radius. Used to locate extremum points.  Clipped to ``[1, L // 4]`` as in the reference; at most 128.
+    sensitive : float
+        To detect extremum points against random noise. Smaller is more sensitive.  A Python float is rounded to the profile's type,
+        a NumPy float64 scalar promotes the comparison, as NumPy 2 compares them.
+    denoise : bool, optional
+        Applying a smoothing filter if True: this module's :func:`gaussian_filter` along the rows, sigma 3.
+    norm : bool, optional
+        Apply background normalization to the array: the reference's sorted-background line fit, row by row in NumPy.
+    subpixel : bool, optional
+        Locate points with subpixel accuracy (the closed form of :func:`locate_subpixel_point`, in the kernel).
+    select_peaks : bool, optional
+        Not implemented (a ``curve_fit`` per peak on the host): True raises ``NotImplementedError``.
+
+    Returns
+    -------
+    array_like
+        1D array. Positions of local extremum points.  For a batch: a list of N such arrays.
+    """
+    if select_peaks is True:
+        raise NotImplementedError("get_local_extrema_points: select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    rows, single = _profile_rows(list_data, "get_local_extrema_points")
+    nrows, num_point = rows.shape
+    radius = int(np.clip(radius, 1, num_point // 4))
+    if radius > PEAK_MAX_RADIUS:
+        raise NotImplementedError("get_local_extrema_points: a search radius above %d is not implemented on the GPU path (got %d)"
+                                  % (PEAK_MAX_RADIUS, radius))
+    if nrows == 0 or num_point == 0:
+        return np.asarray([]) if single else [np.asarray([]) for _ in range(nrows)]
+    if denoise is True:
+        rows = gaussian_filter(rows, (0, 3))
+    if option == "max":
+        rows = np.max(rows, axis=1, keepdims=True) - rows
+    if norm is True:
+        rows = np.asarray([_normalize_background(row) for row in rows])
+    in_kernel = subpixel is True and radius >= 1
+    found = np.empty((nrows, num_point))
+    F.require_device()
+    img = _rows_image(rows)
+    F.check(F.lib().dcp_local_extrema_rows(img.ptr, found.ctypes.data, nrows, num_point, _row_stride(img), img.code, radius,
+                                           _thres_double(sensitive, rows.dtype.name), 1 if in_kernel else 0, img.mem, img.device, img.stream))
+    results = []
+    for p in range(nrows):
+        count = int(found[p, -1])
+        if count == 0:
+            results.append(np.asarray([]))
+        elif subpixel is True:
+            if in_kernel:
+                results.append(found[p, :count].copy())
+            else:       # (rows of fewer than 4 samples, where the radius clips to 0: the reference's loop, on the host)
+                results.append(np.asarray([i - 1 + locate_subpixel_point(rows[p, i - 1:i + 2], option="min") for i in found[p, :count].astype(np.int64)]))
+        else:
+            results.append(found[p, :count].astype(np.int64))
+    return results[0] if single else results
+
+
+def _cross_points(mat, slope, dist, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, across_hor):
+    """The body the two cross-point functions share; across_hor: the generated lines run horizontally (``get_cross_points_ver_lines``)."""
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    mat, kind = _as_kind(mat, "the cross-point functions take NumPy arrays and torch tensors")
+    if len(mat.shape) != 2:
+        raise ValueError("Input must be a 2D array !!!")
+    (height, width) = mat.shape
+    if bgr == "bright":
+        mat = (mat.max() - mat) if kind == "torch" else (np.max(mat) - mat)
+    if norm is True:
+        mat = normalization_fft(mat, 5)
+    if denoise is True:
+        mat = gaussian_filter(mat, 3)
+    angle = np.arctan(slope)
+    if across_hor:
+        angle_deg, direction = -np.rad2deg(angle), "horizontal"
+        first, last = _calc_index_range(height, width, angle_deg, direction=direction)
+        offset = int(np.clip(offset, 0, min(height, width) // 8))
+    else:
+        angle_deg, direction = np.rad2deg(angle), "vertical"
+        first, last = _calc_index_range(height, width, angle_deg, direction=direction)
+        offset = int(np.clip(offset, 0, min(height, width) // 3))
+    indices = np.arange(first + offset, last - offset, ratio * dist)
+    xlists, ylists, profiles = get_tilted_profiles(mat, indices, angle_deg, direction)
+    if kind == "torch":
+        profiles = profiles.cpu().numpy()
+    if len(indices) == 0:
+        return np.asarray([])
+    if chessboard is True:
+        profiles = sliding_window_slope(profiles, size=3)
+    rlists = get_local_extrema_points(profiles, option="max", radius=radius, sensitive=sensitive, denoise=not denoise, norm=not norm,
+                                      subpixel=subpixel)
+    list_points = []
+    for xlist, ylist, rlist in zip(xlists, ylists, rlists):
+        scale = np.sqrt((xlist[-1] - xlist[0]) ** 2 + (ylist[-1] - ylist[0]) ** 2) / ((width if across_hor else height) - 1)
+        rlist = rlist * scale
+        if across_hor:
+            xlist1 = rlist * np.cos(angle) + xlist[0]
+            ylist1 = rlist * np.sin(angle) + ylist[0]
+        else:
+            xlist1 = rlist * np.sin(angle) + xlist[0]
+            ylist1 = rlist * np.cos(angle) + ylist[0]
+        list_points.extend(np.asarray(list(zip(ylist1, xlist1))))
+    return np.asarray(list_points)
+
+
+def get_cross_points_hor_lines(mat, slope_ver, dist_ver, ratio=0.3, norm=True, offset=0, bgr="bright", radius=11, sensitive=0.1,
+                               denoise=True, subpixel=True, chessboard=False, select_peaks=False, **kwargs):
+    """
+    Get points on horizontal lines of a line-pattern image, or a chessboard image, by intersecting with a list of generated
+    vertical-lines (reference ``linepattern.py:604-681``).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array, or a torch tensor on a ROCm device (it stays there up to the profiles).
+    slope_ver : float
+        Representative slope of vertical lines.
+    dist_ver : float
+        Representative distance between vertical lines.
+    ratio : float
+        To adjust the distance (=ratio * dist_ver) between generated lines to create more or fewer lines.
+    norm : bool, optional
+        Apply background normalization to the array.
+    offset : int
+        Starting index of generated lines.
+    bgr : {"bright", "dark"}
+        Specify the brightness of the background relative to the lines.
+    radius : int
+        Search radius. Used to locate extremum points.
+    sensitive : float
+        To detect extremum points against random noise. Smaller is more sensitive.
+    denoise : bool, optional
+        Applying a smoothing filter if True.
+    subpixel : bool, optional
+        Locate points with subpixel accuracy.
+    chessboard : bool, optional
+        If True, cross points are located by finding local maxima of slopes of local linear fits of the generated lines.
+    select_peaks : bool, optional
+        Not implemented: True raises ``NotImplementedError``.
+
+    Returns
+    -------
+    array_like
+        List of (y,x)-coordinates of points: an (N, 2) NumPy array in the reference's order.  ``max - mat``,
+        :func:`~discorpy_amd.prep.preprocessing.normalization_fft`, :func:`gaussian_filter`, all profiles
+        (:func:`get_tilted_profiles`), the slopes and the peak search run on the GPU; the scale and rotation of the positions are NumPy's.
+    """
+    return _cross_points(mat, slope_ver, dist_ver, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, False)
+
+
+def get_cross_points_ver_lines(mat, slope_hor, dist_hor, ratio=0.3, norm=True, offset=0, bgr="bright", radius=11, sensitive=0.1,
+                               denoise=True, subpixel=True, chessboard=False, select_peaks=False, **kwargs):
+    """
+    Get points on vertical lines of a line-pattern image, or a chessboard image, by intersecting with a list of generated
+    horizontal-lines (reference ``linepattern.py:684-761``).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array, or a torch tensor on a ROCm device (it stays there up to the profiles).
+    slope_hor : float
+        Representative slope of horizontal lines.
+    dist_hor : float
+        Representative distance between horizontal lines.
+    ratio : float
+        To adjust the distance (=ratio * dist_hor) between generated lines to create more or fewer lines.
+    norm : bool, optional
+        Apply background normalization to the array.
+    offset : int
+        Starting index of generated lines.
+    bgr : {"bright", "dark"}
+        Specify the brightness of the background against the lines.
+    radius : int
+        Search radius. Used to locate extremum points.
+    sensitive : float
+        To detect extremum points against random noise. Smaller is more sensitive.
+    denoise : bool, optional
+        Applying a smoothing filter if True.
+    subpixel : bool, optional
+        Locate points with subpixel accuracy.
+    chessboard : bool, optional
+        If True, cross points are located by finding local maxima of slopes of local linear fits of the generated lines.
+    select_peaks : bool, optional
+        Not implemented: True raises ``NotImplementedError``.
+
+    Returns
+    -------
+    array_like
+        List of (y,x)-coordinates of points: an (N, 2) NumPy array in the reference's order; see :func:`get_cross_points_hor_lines`.
+    """
+    return _cross_points(mat, slope_hor, dist_hor, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, True)

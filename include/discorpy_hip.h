@@ -617,6 +617,38 @@ int dcp_clear_border_2d(const void* src, uint8_t* dst, int height, int width, lo
 int dcp_morph_cross_2d(const uint8_t* src, uint8_t* dst, int height, int width, long src_row_stride, int op, int mem_kind, int device,
                        void* stream);
 
+/* ---- the per-profile steps of the line-pattern route on batches of profiles (discorpy/prep/linepattern.py:46-274, 512-567) ----
+ * The first two take `nrows` profiles of `length` samples as the rows of a DCP_DTYPE_FLOAT32 / FLOAT64 plane (rows `src_row_stride`
+ * elements apart) and the mem_kind / device / stream triple of dcp_label_2d.
+ *
+ * dcp_local_extrema_rows: the minima search of get_local_extrema_points (after its denoise / option / norm steps).  Sample i of
+ * range(radius, length - radius - 1) is a point iff it equals the minimum of its window [i - radius, i + radius], the window holds no
+ * NaN, and |(v - m) / m| > sensitive, m = np.mean(np.sort(window)[-radius:]) bit for bit (NumPy's pairwise sum in ascending order, then
+ * one division; the quotient counts as 0 where m == 0); all in the profiles' own type, the last comparison in double (`sensitive`
+ * rounded to float32 by the caller gives NumPy's float32 comparison).  dst: (nrows, length) doubles; row r holds its positions in
+ * ascending order and their number in element length - 1 (there are at most length - 1).  subpixel = 1: each position i becomes
+ * i - 1 + (-b / (2 a)) with a = (d0 - 2 d1 + d2) / 2, b = (-3 d0 + 4 d1 - d2) / 2 over d = profile[i - 1 .. i + 1] in double, where a != 0
+ * and the vertex lies in [0, 3), else i - 1 + argmin(d) -- the closed form of the reference's np.polyfit; needs radius >= 1.
+ * 0 <= radius <= 128 (above: DCP_ERR_UNSUPPORTED).
+ *
+ * dcp_window_slope_rows: sliding_window_slope before its division by the mean: dst ((nrows, length), the profiles' type) = the absolute
+ * slope of the least-squares line through the `size` samples (odd, >= 3) around every sample of the edge-padded row,
+ * sum_k (k - r) p[i + k - r] / sum_k (k - r)^2 with products and sum in double (k ascending), rounded to the type.  nrows <= 65535.
+ *
+ * dcp_tilted_profiles_2d: `nprofiles` calls of get_tilted_profile on one height x width plane (FLOAT32 / FLOAT64) in one.  Profile p is
+ * scipy.ndimage.map_coordinates(band_p, ..., order=3, mode="nearest") of its own band -- rows (direction 0) or columns (direction 1)
+ * band_lo[p] .. band_lo[p] + band_count[p] - 1 of the plane -- at the `length` IMAGE coordinates (ycoords, xcoords)[p][i]: doubles that
+ * live where the plane lives, (nprofiles, length) each.  band_lo / band_count are host arrays.  dst: (nprofiles, length) of the plane's
+ * type.  The coefficient planes of the bands come from the library's workspace; above 512 MiB the profiles run in groups.  For
+ * DCP_MEM_DEVICE the call synchronises `stream` once per group (the band table is copied from host memory). */
+int dcp_local_extrema_rows(const void* src, double* dst, int nrows, int length, long src_row_stride, int dtype, int radius, double sensitive,
+                           int subpixel, int mem_kind, int device, void* stream);
+int dcp_window_slope_rows(const void* src, void* dst, int nrows, int length, long src_row_stride, int dtype, int size, int mem_kind, int device,
+                          void* stream);
+int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, int direction, int nprofiles,
+                           int length, const double* ycoords, const double* xcoords, const int32_t* band_lo, const int32_t* band_count,
+                           int mem_kind, int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the

@@ -857,4 +857,190 @@ def g26():
 
 
 g26()
+
+
+# ---- g27: the cross-point route of prep.linepattern (get_local_extrema_points, sliding_window_slope, get_cross_points_hor_lines /
+# get_cross_points_ver_lines): what the reference's own functions return (skimage stubbed as for g26), for the peak tables, the slope rows
+# and the image cases of tests/test_cross_points_{cpu,gpu}.py.  Images are stored as float32; a float64 case is their cast.
+def g27_tables():
+    rng = np.random.default_rng(2727)
+    tables = []          # (row, radius, sensitive)
+
+    def add(row, radii, sensitive=0.1):
+        for r in radii:
+            tables.append((row, r, sensitive))
+    for dt in (np.float32, np.float64):
+        for n in (1, 2, 3, 4, 5, 8):
+            add(rng.integers(0, 6, n).astype(dt), (1, 5))
+        for n in (255, 256, 257, 513):
+            radii = (1, 5, 11, 63, 128)
+            add(rng.integers(1, 10, n).astype(dt), radii)                                     # small integers: ties, every sum exact
+            x = np.arange(n)
+            add((2.0 + np.cos(x * 2 * np.pi / 37.3) + 0.05 * rng.standard_normal(n)).astype(dt), radii)
+            add((2.0 + np.cos(x * 2 * np.pi / 37.3) + 0.05 * rng.standard_normal(n)).astype(dt), (5, 11), np.float64(0.3))   # promotes
+        plateau = np.full(257, 4.0)
+        plateau[20:27] = 1.0                                                                  # a flat minimum: every sample of it is a point
+        plateau[100:102] = 2.0
+        plateau[180] = 3.0
+        plateau[181] = 3.0
+        add(plateau.astype(dt), (1, 5, 11))
+        withnan = (3.0 + np.sin(np.arange(256) / 5.0)).astype(dt)
+        withnan[77] = np.nan
+        add(withnan, (1, 5, 11, 63))
+        zeros = np.zeros(255)
+        zeros[40::30] = -1.0                                                                  # the largest elements are all 0: m == 0
+        add(zeros.astype(dt), (1, 5, 11))
+        exact = np.full(256, 2.0)
+        exact[30::40] = 1.0                                                                   # |(1 - 2) / 2| = 0.5 exactly
+        add(exact.astype(dt), (1, 5, 11), 0.5)
+        add(exact.astype(dt), (5,), 0.25)
+    return tables
+
+
+def g27_images():
+    rng = np.random.default_rng(2728)
+
+    def grid(shape, dist, deg, chess):
+        h, w = shape
+        y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+        t = np.deg2rad(deg)
+        u, v = x * np.cos(t) + y * np.sin(t) + 7.3, -x * np.sin(t) + y * np.cos(t) + 11.9
+        ramp = 0.75 + 0.2 * x / w + 0.1 * y / h
+        if chess:
+            img = ((np.floor(u / dist) + np.floor(v / dist)) % 2) * 0.8 + 0.1
+            img = ndi.gaussian_filter(img, 1.0)
+        else:
+            du, dv = (u + dist / 2) % dist - dist / 2, (v + dist / 2) % dist - dist / 2
+            img = 1.0 - 0.8 * np.maximum(np.exp(-du * du / (2 * 1.6 ** 2)), np.exp(-dv * dv / (2 * 1.6 ** 2)))
+        return (img * ramp * (1.0 + 0.01 * rng.standard_normal(shape))).astype(np.float32)
+    return dict(line=grid((160, 200), 20, 1.5, False), chess=grid((160, 200), 24, 1.5, True), tall=grid((300, 96), 20, 1.5, False))
+
+
+def g27():
+    import types
+    import warnings
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    sys.modules["skimage.filters"].threshold_otsu = None
+    sys.modules["skimage.segmentation"].clear_border = None
+    sys.modules["skimage.transform"].radon = None
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import discorpy.prep.linepattern as rlp
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import peaks_reference as pr
+    out = {}
+    e_sub, e_slope = 0.0, 0.0
+    # -- peak tables
+    tables = g27_tables()
+    out["pk_radius"] = np.array([t[1] for t in tables], np.int64)
+    out["pk_sensitive"] = f64([t[2] for t in tables])
+    out["pk_promotes"] = np.array([isinstance(t[2], np.float64) for t in tables])
+    for k, (row, radius, sensitive) in enumerate(tables):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ints = rlp.get_local_extrema_points(row, option="min", radius=radius, sensitive=sensitive, denoise=False, norm=False, subpixel=False)
+            subs = rlp.get_local_extrema_points(row, option="min", radius=radius, sensitive=sensitive, denoise=False, norm=False, subpixel=True)
+        ints = np.asarray(ints, np.int64)
+        subs = f64(subs)
+        assert len(ints) == len(subs)
+        # a flat triple has no parabola: the polyfit's rounding noise decides there, the closed form says argmin (not compared)
+        curved = np.array([not (row[i - 1] == row[i] == row[i + 1]) for i in ints], bool)
+        if curved.any():
+            e_sub = max(e_sub, float(np.abs(pr.refine(row, ints)[curved] - subs[curved]).max()))
+        out["pk%d_row" % k], out["pk%d_int" % k], out["pk%d_sub" % k], out["pk%d_curved" % k] = row, ints, subs, curved
+    out["pk_count"] = np.int64(len(tables))
+    assert sum(len(out["pk%d_int" % k]) for k in range(len(tables))) > 300
+    # -- rows through denoise and norm
+    rng = np.random.default_rng(2729)
+    dn = []
+    for dt in (np.float32, np.float64):
+        for n in (257, 513):
+            x = np.arange(n)
+            dn.append(((3.0 + 0.004 * x - 2.5 * np.exp(-(((x + 20) % 41.7) - 20) ** 2 / 18.0) + 0.05 * rng.standard_normal(n)).astype(dt), 11))   # narrow dips
+    for k, (row, radius) in enumerate(dn):
+        ints = np.asarray(rlp.get_local_extrema_points(row, radius=radius, subpixel=False), np.int64)
+        subs = f64(rlp.get_local_extrema_points(row, radius=radius, subpixel=True))
+        assert len(ints) > 4 and len(ints) == len(subs)
+        out["dn%d_row" % k], out["dn%d_int" % k], out["dn%d_sub" % k] = row, ints, subs
+    out["dn_count"], out["dn_radius"] = np.int64(len(dn)), np.int64(11)
+    # -- slope rows
+    sl = [(2.0 + np.cos(np.arange(257) / 6.0) + 0.05 * rng.standard_normal(257)), rng.integers(0, 9, 8).astype(np.float64)]
+    for k, row in enumerate(sl):
+        out["sl%d_row" % k] = row
+        for size in (3, 5):
+            raw = rlp.sliding_window_slope(row, size=size, norm=False)
+            out["sl%d_s%d" % (k, size)] = raw
+            out["sl%d_s%d_norm" % (k, size)] = rlp.sliding_window_slope(row, size=size, norm=True)
+            e_slope = max(e_slope, float(np.abs(pr.window_slope(row, size) - raw).max() / np.abs(raw).max()))
+    out["sl_count"] = np.int64(len(sl))
+    # -- images
+    images = g27_images()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        images["chess"] = rlp.convert_chessboard_to_linepattern(images["chess"].astype(np.float64)).astype(np.float32)
+    for name, img in images.items():
+        out["img_" + name] = img
+    slope = float(np.tan(np.deg2rad(1.5)))
+    flags = [("default", "line", {}), ("nonorm", "line", dict(norm=False)), ("nodenoise", "line", dict(denoise=False)),
+             ("dark", "line", dict(bgr="dark")), ("offset", "line", dict(offset=9)), ("chess", "chess", dict(chessboard=True))]
+    names, noise_rng = [], np.random.default_rng(2730)
+
+    def profiles_of(mat, hor, kw):                                  # the reference's body up to the profiles, for the margin check
+        bgr, norm, denoise, offset = kw.get("bgr", "bright"), kw.get("norm", True), kw.get("denoise", True), kw.get("offset", 0)
+        (height, width) = mat.shape
+        if bgr == "bright":
+            mat = np.max(mat) - mat
+        if norm is True:
+            mat = rlp.prep.normalization_fft(mat, 5)
+        if denoise is True:
+            mat = ndi.gaussian_filter(mat, 3)
+        angle = np.arctan(slope)
+        if hor:
+            lo, hi = rlp._calc_index_range(height, width, np.rad2deg(angle), direction="vertical")
+            offset = int(np.clip(offset, 0, min(height, width) // 3))
+            return [rlp.get_tilted_profile(mat, i, np.rad2deg(angle), direction="vertical")[2] for i in np.arange(lo + offset, hi - offset, 0.3 * dist)]
+        lo, hi = rlp._calc_index_range(height, width, -np.rad2deg(angle), direction="horizontal")
+        offset = int(np.clip(offset, 0, min(height, width) // 8))
+        return [rlp.get_tilted_profile(mat, i, -np.rad2deg(angle), direction="horizontal")[2] for i in np.arange(lo + offset, hi - offset, 0.3 * dist)]
+    for dt in ("float32", "float64"):
+        for flag, key, kw in flags:
+            dist = 24.0 if key == "chess" else 20.0
+            mat = images[key].astype(dt)
+            if flag == "dark":
+                mat = mat.max() - mat
+            for fn in ("hor", "ver"):
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    ref_fn = rlp.get_cross_points_hor_lines if fn == "hor" else rlp.get_cross_points_ver_lines
+                    pts = ref_fn(mat, slope, dist, **kw)
+                    name = "%s_%s_%s" % (flag, dt, fn)
+                    assert pts.ndim == 2 and len(pts) >= 50, (name, pts.shape)
+                    for prof in profiles_of(mat, fn == "hor", kw):
+                        if kw.get("chessboard"):
+                            prof = rlp.sliding_window_slope(prof, size=3)
+                        args = dict(option="max", radius=11, sensitive=0.1, denoise=not kw.get("denoise", True), norm=not kw.get("norm", True),
+                                    subpixel=False)
+                        a = rlp.get_local_extrema_points(prof, **args)
+                        b = rlp.get_local_extrema_points(prof * (1 + 1e-9 * noise_rng.standard_normal(len(prof))), **args)
+                        assert np.array_equal(a, b), (name, a, b)
+                        if len(a):                     # the sub-pixel closed form against the polyfit on the profile the reference searched
+                            d = np.copy(prof)
+                            if args["denoise"]:
+                                d = ndi.gaussian_filter(d, 3)
+                            d = np.max(d) - d
+                            if not args["norm"]:
+                                sub = rlp.get_local_extrema_points(prof, **dict(args, subpixel=True))
+                                e_sub = max(e_sub, float(np.abs(pr.refine(d, np.asarray(a, np.int64)) - sub).max()))
+                names.append(name)
+                out["pts_" + name] = pts
+    out["case_names"] = np.array(names)
+    out["slope"], out["e_sub"], out["e_slope"] = np.float64(slope), np.float64(e_sub), np.float64(e_slope)
+    assert e_sub < 1e-9 and e_slope < 1e-12, (e_sub, e_slope)
+    print("g27: %d tables, %d image cases, e_sub %.3g, e_slope %.3g" % (len(tables), len(names), e_sub, e_slope))
+    save("g27_cross_points", **out)
+    assert os.path.getsize(os.path.join(OUT, "g27_cross_points.npz")) <= os.path.getsize(os.path.join(OUT, "g26_fourier_gauss.npz"))
+
+
+g27()
 print("done")

@@ -27,6 +27,17 @@ axis, the fused multiply-adds that makes and the rate it amounts to; with scipy 
 the difference of the outputs.  There is no threshold: the numbers go to DESIGN.md as they are.
 
     python tools/time_gaussian.py --fourier [--cases 2000:10:100,2000:5:100,4096:10:100] [--rounds 5] [--reps 10] [--no-scipy]
+
+--cross-points: the whole line-pattern route, with options of its own.  Time prep.linepattern.get_cross_points_hor_lines on an
+1800 x 2000 float32 line pattern (line distance 90, tilted 1.5 degrees, default arguments) for NumPy and for tensor input (wall clock:
+the call ends on the host), and each of its GPU steps on the device tensor between device events: max - mat, normalization_fft(mat, 5),
+gaussian_filter(mat, 3), get_tilted_profiles (its host part -- the coordinates -- on the wall clock beside it) and the peak search
+(dcp_local_extrema_rows on device-resident profiles; the wrapper on host rows on the wall clock).  Warm-up calls, then `--rounds` (at
+least five) rounds of `--reps` calls; the median round and the range are printed in ms per call.  The NumPy restatement of the peak
+search (tests/helpers/peaks_reference.py: the reference's loop with the sort of candidate windows only) is timed once on the same
+profiles, on this machine's CPU, and its positions are compared with the kernel's.
+
+    python tools/time_gaussian.py --cross-points [--shape 1800x2000] [--dist 90] [--rounds 5] [--reps 5] [--no-numpy]
 """
 import argparse
 import os
@@ -44,6 +55,8 @@ MODE_NEAREST = 4        # DCP_MODE_NEAREST
 def main():
     if "--fourier" in sys.argv[1:]:
         return fourier_main([v for v in sys.argv[1:] if v != "--fourier"])
+    if "--cross-points" in sys.argv[1:]:
+        return cross_points_main([v for v in sys.argv[1:] if v != "--cross-points"])
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
     ap.add_argument("--dtypes", default="float32,uint16")
@@ -221,6 +234,98 @@ def fourier_main(argv):
             line += "  scipy.fftpack on the host %9.1f ms  ratio %7.1f  |difference| / max %.2e" % (
                 cpu_ms, cpu_ms / med["toeplitz"], np.abs(got["toeplitz"] - ref).max() / np.abs(ref).max())
         print(line + "  [%s]" % kernels, flush=True)
+
+
+def cross_points_main(argv):
+    ap = argparse.ArgumentParser(prog="time_gaussian.py --cross-points", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shape", default="1800x2000")
+    ap.add_argument("--dist", type=float, default=90.0)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--no-numpy", action="store_true", help="skip the NumPy restatement of the peak search")
+    a = ap.parse_args(argv)
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    import torch
+    from discorpy_amd import _ffi as F
+    from discorpy_amd.prep import linepattern as lp
+    from discorpy_amd.prep import preprocessing as prep
+    F.require_device()
+    height, width = (int(v) for v in a.shape.split("x"))
+    rng = np.random.default_rng(13)
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    tilt = np.deg2rad(1.5)
+    u, v = x * np.cos(tilt) + y * np.sin(tilt) + 7.3, -x * np.sin(tilt) + y * np.cos(tilt) + 11.9
+    du, dv = (u + a.dist / 2) % a.dist - a.dist / 2, (v + a.dist / 2) % a.dist - a.dist / 2
+    img = 1.0 - 0.8 * np.maximum(np.exp(-du * du / (2 * 2.5 ** 2)), np.exp(-dv * dv / (2 * 2.5 ** 2)))
+    img = (img * (0.75 + 0.2 * x / width + 0.1 * y / height) * (1.0 + 0.01 * rng.standard_normal(img.shape))).astype(np.float32)
+    slope = float(np.tan(tilt))
+    t = torch.from_numpy(img).to("cuda:0")
+
+    def wall(fn):
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / a.reps
+
+    def events(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / a.reps
+
+    def report(label, timer, fn):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        rounds = [timer(fn) for _ in range(a.rounds)]
+        print("%-74s %9.4f ms (rounds %.4f .. %.4f)" % (label, float(np.median(rounds)), min(rounds), max(rounds)), flush=True)
+        return float(np.median(rounds))
+    points = lp.get_cross_points_hor_lines(img, slope, a.dist)
+    print("float32 %d x %d, line distance %g: %d points" % (height, width, a.dist, len(points)), flush=True)
+    report("get_cross_points_hor_lines, NumPy input (wall clock)", wall, lambda: lp.get_cross_points_hor_lines(img, slope, a.dist))
+    report("get_cross_points_hor_lines, tensor input (wall clock)", wall, lambda: lp.get_cross_points_hor_lines(t, slope, a.dist))
+    inv = t.max() - t
+    nrm = prep.normalization_fft(inv, 5)
+    den = lp.gaussian_filter(nrm, 3)
+    angle = np.rad2deg(np.arctan(slope))
+    first, last = lp._calc_index_range(height, width, angle, "vertical")
+    indices = np.arange(first, last, 0.3 * a.dist)
+    report("max - mat (device events)", events, lambda: t.max() - t)
+    report("normalization_fft(mat, 5) (device events)", events, lambda: prep.normalization_fft(inv, 5))
+    report("gaussian_filter(mat, 3) (device events)", events, lambda: lp.gaussian_filter(nrm, 3))
+    report("get_tilted_profiles, %d profiles of %d (device events)" % (len(indices), height), events,
+           lambda: lp.get_tilted_profiles(den, indices, angle, "vertical"))
+    kernels = F.last_kernel()
+    report("get_tilted_profiles, with its coordinates on the host (wall clock)", wall, lambda: lp.get_tilted_profiles(den, indices, angle, "vertical"))
+    profiles = lp.get_tilted_profiles(den, indices, angle, "vertical")[2]
+    rows = profiles.max(dim=1, keepdim=True).values - profiles                   # option="max"
+    found = torch.empty(rows.shape, dtype=torch.float64, device=rows.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    report("peak search, %d x %d device-resident rows, radius 11, sub-pixel (device events)" % tuple(rows.shape), events,
+           lambda: F.check(F.lib().dcp_local_extrema_rows(rows.data_ptr(), found.data_ptr(), rows.shape[0], rows.shape[1], rows.shape[1],
+                                                          F.DTYPE_BY_NAME["float64"], 11, 0.1, 1, F.MEM_DEVICE, -1, stream)))
+    kernels += " | " + F.last_kernel()
+    host_rows = profiles.cpu().numpy()
+    report("get_local_extrema_points on host rows (wall clock)", wall,
+           lambda: lp.get_local_extrema_points(host_rows, option="max", radius=11, denoise=False, norm=False))
+    if not a.no_numpy:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "helpers"))
+        import peaks_reference as PR
+        flipped = np.max(host_rows, axis=1, keepdims=True) - host_rows
+        t0 = time.perf_counter()
+        restated = [PR.local_minima(row, 11, 0.1) for row in flipped]
+        cpu_ms = (time.perf_counter() - t0) * 1e3
+        got = lp.get_local_extrema_points(host_rows, option="max", radius=11, denoise=False, norm=False, subpixel=False)
+        same = all(np.array_equal(g, r) for g, r in zip(got, restated))
+        print("%-74s %9.1f ms (once; %d points, equal to the kernel's: %s)" % ("NumPy restatement of the peak search on this machine's CPU", cpu_ms,
+                                                                               sum(len(r) for r in restated), same), flush=True)
+    print("[%s]" % kernels, flush=True)
 
 
 if __name__ == "__main__":
