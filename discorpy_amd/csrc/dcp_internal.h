@@ -321,6 +321,16 @@ size_t profile_band_elems(int H, int W, bool vertical, int n);
 hipError_t launch_tilted_profiles(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, bool vertical, int nprof, int len,
                                   const double* ycoord, const double* xcoord, const int32_t* band_lo, const int32_t* band_n, void* work, size_t work_bytes,
                                   hipStream_t stream);
+// radon_kernels.hip: the sinogram of the N x N plane at src (kF32 / kF64, rows `src_stride` elements apart) for `nangles` angles, as
+// DESIGN.md ("Radon transform") defines it: the plane zeroed outside its inscribed circle, rotated about (N / 2, N / 2) by bilinear
+// interpolation with zeros outside, and summed over the rows in ascending order, all in float64.  table: HOST array of {cos a, sin a,
+// tx, ty} per angle.  dst: dense (N, nangles) doubles.  `work`: radon_work_bytes(nangles) of device memory.
+// THE STREAM IS SYNCHRONISED once, after the table has been copied and before the kernel is enqueued.
+constexpr int kRadonMaxSide = 32768;           // with kRadonMaxAngles: N * nangles < 2^31, (N / 2)^2 * 2 < 2^31, every index fits int32
+constexpr int kRadonMaxAngles = 65535;         // one angle per blockIdx.y
+inline size_t radon_work_bytes(int nangles) { return (size_t)nangles * 4 * sizeof(double); }
+hipError_t launch_radon(const void* src, double* dst, int N, int64_t src_stride, int dtype, int nangles, const double* table, void* work,
+                        hipStream_t stream);
 // label_kernels.hip: connected components of the nonzero pixels (any ElemType; floats by their bits: NaN is set, -0.0 is not) numbered
 // as scipy.ndimage.label numbers them, into dst (dense H x W int32, 0 = background).  conn8: the full 3 x 3 structure, else the cross.
 // `parent`: H W int32 of device scratch, `counts`: label_count_words(H, W) more; the number of labels is left in the LAST word of

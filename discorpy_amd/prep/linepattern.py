@@ -29,9 +29,19 @@ noise can leave ``a`` nonzero where the closed form gives ``a == 0`` and falls b
 the minimum test, the mean of the ``radius`` largest window elements (NumPy's pairwise sum, restated bit for bit) and the sensitivity
 quotient are evaluated in the profile's own type as NumPy 2 evaluates them.
 
-Out of scope: the selection of good peaks behind the peak search (``select_good_peaks``: a scipy ``curve_fit`` per peak) and the Radon
-functions (``calc_slope_distance_hor_lines`` / ``calc_slope_distance_ver_lines``: scikit-image): a caller passes the slope and the
-distance to the cross-point functions, as the reference's signature has it.
+* :func:`radon`   ``skimage.transform.radon(image, theta, circle=True)`` restated from its documentation (``dcp_radon_2d``; the kernel is
+  in ``csrc/radon_kernels.hip``): all angles in one launch, float64, equal bit for bit to the NumPy restatement of its definition
+  (``DESIGN.md``, "Radon transform"; ``tests/helpers/radon_reference.py``).  scikit-image is not installed where this was written, so
+  agreement with scikit-image itself is UNVERIFIED
+* :func:`calc_slope_distance_hor_lines`, :func:`calc_slope_distance_ver_lines`, :func:`_make_circle_mask`   reference
+  ``linepattern.py:277-449``: same names, arguments and defaults, step for step; the Gaussian, the two sinograms, their maxima and the
+  peak search run on the GPU.  They give the ``slope_*`` and ``dist_*`` the cross-point functions take
+
+These names are listed in :data:`RADON`.
+
+Out of scope: the selection of good peaks behind the peak search (``select_good_peaks``: a scipy ``curve_fit`` per peak), so
+``select_peaks=True`` raises ``NotImplementedError`` in the peak search and in the Radon slope functions alike, and ``circle=False`` of
+the Radon transform, which raises too.
 
 The Gaussian runs as hand-written HIP kernels through ``dcp_correlate_sym_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/gauss_kernels.hip``) with scipy's arithmetic restated operation by operation (``DESIGN.md``), so the result equals scipy's bit
@@ -50,9 +60,12 @@ import numpy as np
 
 from .. import _ffi as F
 from ..post.postprocessing import _Image, _MODES, remap_coordinates
-from .preprocessing import _as_kind, _is_complex, _row_stride, _rows_image, _thres_double, normalization_fft
+from .preprocessing import _as_kind, _is_complex, _new_like, _row_stride, _rows_image, _select_roi, _thres_double, normalization_fft
 
 __all__ = ["gaussian_filter", "convert_chessboard_to_linepattern", "get_tilted_profile"]
+# the slope and distance search in front of the cross-point route, and the Radon transform it rests on
+RADON = ["radon", "calc_slope_distance_hor_lines", "calc_slope_distance_ver_lines"]
+RADON_MAX_SIDE, RADON_MAX_ANGLES = 32768, 65535       # dcp_radon_2d: every index of the kernel fits 32 bits
 # the cross-point route (batched profiles, the peak search and the reference's two functions on top of them)
 CROSS_POINTS = ["get_tilted_profiles", "sliding_window_slope", "locate_subpixel_point", "get_local_extrema_points",
                 "get_cross_points_hor_lines", "get_cross_points_ver_lines"]
@@ -679,3 +692,248 @@ def get_cross_points_ver_lines(mat, slope_hor, dist_hor, ratio=0.3, norm=True, o
         List of (y,x)-coordinates of points: an (N, 2) NumPy array in the reference's order; see :func:`get_cross_points_hor_lines`.
     """
     return _cross_points(mat, slope_hor, dist_hor, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, True)
+
+
+# --------------------------------------------------------------------------- the Radon transform and the slope and distance search
+
+def _radon_table(theta, side):
+    """(A, 4) float64, C-contiguous: ``cos a, sin a, tx, ty`` of every angle of ``theta`` (degrees) -- the rotation about
+    ``(side // 2, side // 2)`` that ``dcp_radon_2d`` applies, in NumPy float64."""
+    center = side // 2
+    angle = np.deg2rad(np.asarray(theta, dtype=np.float64))
+    cos_a, sin_a = np.cos(angle), np.sin(angle)
+    shift_x = -center * (cos_a + sin_a - 1)
+    shift_y = -center * (cos_a - sin_a - 1)
+    return np.ascontiguousarray(np.stack([cos_a, sin_a, shift_x, shift_y], axis=1))
+
+
+def radon(image, theta=None, circle=True):
+    """
+    Radon transform of a 2D image: ``skimage.transform.radon(image, theta, circle=True)`` restated from its documentation, all angles
+    in one launch of the GPU (``dcp_radon_2d``).  Agreement with scikit-image itself is UNVERIFIED: it is not installed where this was
+    written; the oracle is the NumPy restatement of the definition below (``tests/helpers/radon_reference.py``), which the result
+    equals bit for bit.
+
+    Parameters
+    ----------
+    image : array_like
+        2D array of float32 / float64: a NumPy array, a ROCm torch tensor (zero-copy, on torch's current stream) or a
+        ``__cuda_array_interface__`` device array.  A strided view (a region of interest) is read in place.  A non-square image is
+        cropped to its centred square, each axis starting at ``ceil(excess / 2)``, as a view.  Integer and bool input raise
+        ``NotImplementedError`` (scikit-image would rescale them; that is not imitated), float16 raises ``RuntimeError``, complex
+        input ``TypeError``.
+    theta : array_like, optional
+        Projection angles in degree; ``np.arange(180)`` if None.
+    circle : bool
+        Only True is implemented: the image is zero outside its inscribed circle.  What lies there is replaced by 0.0, not
+        multiplied by it, so a NaN outside the circle does not reach the result.  The warning scikit-image gives for nonzero
+        elements outside the circle is not reproduced.
+
+    Returns
+    -------
+    array_like
+        (N, len(theta)) float64 sinogram of the input's kind, column ``i`` the projection at ``theta[i]``.  With ``c0 = N // 2`` and
+        ``a`` the angle in radian, sample ``(r, c)`` reads the image at ``x = cos(a) c + sin(a) r - c0 (cos(a) + sin(a) - 1)``,
+        ``y = -sin(a) c + cos(a) r - c0 (cos(a) - sin(a) - 1)`` by bilinear interpolation between ``floor`` and ``ceil`` with zeros
+        outside the image, and ``sinogram[c, i]`` is the sum over ``r`` in ascending order.  Everything is float64, also for float32
+        input, where scikit-image would stay in float32: a stated difference.
+    """
+    if _is_complex(image):
+        raise TypeError("Complex type not supported")
+    if circle is not True:
+        raise NotImplementedError("radon: circle=False is not implemented on the GPU path")
+    shape = tuple(image.shape) if hasattr(image, "shape") else np.shape(image)
+    if len(shape) != 2:
+        raise ValueError("The input image must be 2-D")                      # scikit-image's words
+    img = _Image(image, 2)
+    if img.code not in (F.DTYPE_BY_NAME["float32"], F.DTYPE_BY_NAME["float64"]):
+        raise NotImplementedError("radon: element type %s is not implemented on the GPU path (float32 and float64 only; integers are "
+                                  "not rescaled as scikit-image rescales them)" % (img.dtype,))
+    theta = np.arange(180) if theta is None else np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    if theta.ndim != 1:
+        raise ValueError("theta must be a 1D sequence of angles")
+    img = _rows_image(img)
+    side, nangles = min(img.shape), len(theta)
+    if side < 1:
+        raise ValueError("The input image must not be empty")
+    if side > RADON_MAX_SIDE or nangles > RADON_MAX_ANGLES:
+        raise NotImplementedError("radon: a side above %d or more than %d angles is not implemented on the GPU path (got %d, %d)"
+                                  % (RADON_MAX_SIDE, RADON_MAX_ANGLES, side, nangles))
+    table = _radon_table(theta, side)
+    if not np.isfinite(table).all():
+        raise ValueError("theta must be finite")
+    res, optr = _new_like(img, (side, nangles), np.float64)
+    if nangles == 0:
+        return res
+    # the centred square, as a view: a shifted pointer, the same row stride
+    first = [int(np.ceil((n - side) / 2)) for n in img.shape]
+    ptr = img.ptr + (first[0] * img.strides[0] + first[1] * img.strides[1]) * (4 if img.f32 else 8)
+    F.require_device()
+    F.check(F.lib().dcp_radon_2d(ptr, optr, side, img.strides[0] if img.shape[0] > 1 else side, img.code, nangles,
+                                 table.ctypes.data_as(F.C.POINTER(F.C.c_double)), img.mem, img.device, img.stream))
+    return res
+
+
+def _make_circle_mask(width, ratio):
+    """
+    Create a circle mask (reference ``linepattern.py:277-299``).
+
+    Parameters
+    -----------
+    width : int
+        Width of a square array.
+    ratio : float
+        Ratio between the diameter of the mask and the width of the array.
+
+    Returns
+    ------
+    array_like
+         Square array: float32, 1.0 inside the circle, 0.0 outside.
+    """
+    mask = np.zeros((width, width), dtype=np.float32)
+    center = width // 2
+    radius = ratio * center
+    y, x = np.ogrid[-center:width - center, -center:width - center]
+    mask[x * x + y * y <= radius * radius] = 1.0
+    return mask
+
+
+def _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, hor):
+    """The body the two slope functions share; hor: the lines run horizontally (the search is centred on 90 degree)."""
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    if _is_complex(mat):
+        raise TypeError("Complex type not supported")
+    mat, kind = _as_kind(mat, "the slope functions take NumPy arrays and torch tensors")
+    if len(mat.shape) != 2:
+        raise ValueError("Input must be a 2D array !!!")
+    if chessboard is True:
+        if kind == "torch":
+            # (on a host copy: torch sums the conversion's mean in another order, which moved a distance by 1e-7 pixel; the copy
+            # keeps a tensor's result equal to an array's)
+            import torch
+            mat = torch.from_numpy(convert_chessboard_to_linepattern(mat.cpu().numpy())).to(mat.device)
+        else:
+            mat = convert_chessboard_to_linepattern(mat)
+    if denoise is True:
+        mat = gaussian_filter(mat, 3)
+    mat_roi = _select_roi(mat, ratio, square=True)
+    mask = _make_circle_mask(mat_roi.shape[0], 0.92)
+    if kind == "torch":
+        import torch
+        if bgr == "bright":
+            mat_roi = mat_roi.max() - mat_roi
+        masked = mat_roi * torch.from_numpy(mask).to(mat_roi.device)
+
+        def column_maxima(sinogram):
+            return sinogram.amax(dim=0).cpu().numpy()
+    else:
+        if bgr == "bright":
+            mat_roi = np.max(mat_roi) - mat_roi
+        masked = mat_roi * mask
+
+        def column_maxima(sinogram):
+            return np.amax(sinogram, axis=0)
+    angle_coarse = (90.0 if hor else 0.0) + np.arange(-search_range, search_range + 1.0)
+    best_angle1 = angle_coarse[np.argmax(column_maxima(radon(masked, theta=angle_coarse, circle=True)))]
+    angle_fine = np.arange(best_angle1 - 1.0, best_angle1 + 1.05, 0.05)
+    sinogram2 = radon(masked, theta=angle_fine, circle=True)
+    pos_max2 = np.argmax(column_maxima(sinogram2))       # (A numbers: the first of equal maxima, as the reference takes it)
+    best_angle2 = -(angle_fine[pos_max2] - 90) if hor else angle_fine[pos_max2]
+    slope = np.tan(best_angle2 * np.pi / 180.0)
+    profile = sinogram2[:, pos_max2]
+    list_ext_point = get_local_extrema_points(profile.cpu().numpy() if kind == "torch" else profile, option="max", radius=radius,
+                                              denoise=denoise, norm=norm, subpixel=subpixel, sensitive=sensitive)
+    if len(list_ext_point) > 3:
+        distance = np.median(np.abs(np.diff(list_ext_point)))
+    else:
+        distance = np.mean(np.abs(np.diff(list_ext_point)))
+    return slope, distance
+
+
+def calc_slope_distance_hor_lines(mat, ratio=0.3, search_range=30.0, radius=9, sensitive=0.1, bgr="bright", denoise=True, norm=True,
+                                  subpixel=True, chessboard=False, select_peaks=False, **kwargs):
+    """
+    Calculate the representative distance between horizontal lines and the representative slope of these lines using the ROI around
+    the middle of a line-pattern image or a chessboard image (reference ``linepattern.py:302-375``).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array, or a torch tensor on a ROCm device (it stays there up to the best projection).
+    ratio : float
+        Used to select the ROI around the middle of an image.
+    search_range : float
+        Search range in Degree to determine the slope of lines.
+    radius : int
+        Search radius. Used to locate lines.
+    sensitive : float
+        To detect lines against random noise. Smaller is more sensitive.
+    bgr : {"bright", "dark"}
+        Specify the brightness of the background against the lines.
+    denoise : bool, optional
+        Apply a smoothing filter if True.
+    norm : bool, optional
+        Apply background normalization to the array.
+    subpixel : bool, optional
+        Locate points with subpixel accuracy.
+    chessboard : bool, optional
+        If True, converts the input chessboard image to a line-pattern image.  For a tensor the conversion
+        (:func:`convert_chessboard_to_linepattern`) runs on a host copy and goes back to the device: torch sums the conversion's mean
+        in another order than NumPy, and a tensor must give the array's slope and distance.
+    select_peaks : bool, optional
+        Not implemented: True raises ``NotImplementedError``.
+
+    Returns
+    -------
+    slope : float
+        Slope of horizontal lines in Radian.
+    distance : float
+        Distance between horizontal lines.  The reference's steps one for one: :func:`gaussian_filter`, the square ROI, ``max - roi``,
+        the circle mask, a coarse sinogram (:func:`radon`) over ``90 + arange(-search_range, search_range + 1)`` degree, a fine one in
+        steps of 0.05 degree around its best angle, and :func:`get_local_extrema_points` on the best projection.  The elementwise
+        steps are NumPy's or torch's by the input's kind; the maxima over a projection are taken where the sinogram lives.  The
+        sinograms are float64 also for float32 images (:func:`radon`).
+    """
+    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, True)
+
+
+def calc_slope_distance_ver_lines(mat, ratio=0.3, search_range=30.0, radius=9, sensitive=0.1, bgr="bright", denoise=True, norm=True,
+                                  subpixel=True, chessboard=False, select_peaks=False, **kwargs):
+    """
+    Calculate the representative distance between vertical lines and the representative slope of these lines using the ROI around
+    the middle of a line-pattern image or a chessboard image (reference ``linepattern.py:378-449``).
+
+    Parameters
+    ----------
+    mat : array_like
+        2D array.  A NumPy array, or a torch tensor on a ROCm device (it stays there up to the best projection).
+    ratio : float
+        Used to select the ROI around the middle of an image.
+    search_range : float
+        Search range in Degree to determine the slope of lines.
+    radius : int
+        Search radius. Used to locate lines.
+    sensitive : float
+        To detect lines against random noise. Smaller is more sensitive.
+    bgr : {"bright", "dark"}
+        Specify the brightness of the background against the lines.
+    denoise : bool, optional
+        Applying a smoothing filter if True.
+    norm : bool, optional
+        Apply background normalization to the array.
+    subpixel : bool, optional
+        Locate points with subpixel accuracy.
+    chessboard : bool, optional
+        If True, converts the input chessboard image to a line-pattern image.
+    select_peaks : bool, optional
+        Not implemented: True raises ``NotImplementedError``.
+
+    Returns
+    -------
+    slope : float
+        Slope of vertical lines in Radian.
+    distance : float
+        Distance between vertical lines; see :func:`calc_slope_distance_hor_lines` (the search is centred on 0 degree).
+    """
+    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, False)

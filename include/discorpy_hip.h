@@ -649,6 +649,24 @@ int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, lo
                            int length, const double* ycoords, const double* xcoords, const int32_t* band_lo, const int32_t* band_count,
                            int mem_kind, int device, void* stream);
 
+/* ---- the Radon transform behind the slope search of the line-pattern route (discorpy/prep/linepattern.py:302-449) ----
+ * dcp_radon_2d: the sinogram of a side x side plane (DCP_DTYPE_FLOAT32 / FLOAT64, rows `src_row_stride` elements apart, read in place)
+ * for `nangles` angles in one launch; dst: (side, nangles) doubles, row-major.  With c0 = side / 2 (integer division):
+ *   g(y, x)  = (double)src[y, x], and 0.0 where y or x lies outside [0, side) or (y - c0)^2 + (x - c0)^2 > c0^2 (an assignment: a NaN there does not reach dst);
+ *   for angle i, table[4 i .. 4 i + 3] = {ca, sa, tx, ty} (HOST doubles; for an angle a: cos a, sin a, -c0 (ca + sa - 1),
+ *   -c0 (ca - sa - 1)), the sample (r, c) reads x = ca c + sa r + tx, y = -sa c + ca r + ty (left to right, no fused multiply-add),
+ *   x0 = floor x, x1 = ceil x, y0 = floor y, y1 = ceil y, dx = x - x0, dy = y - y0,
+ *   v = (1 - dy) ((1 - dx) g(y0, x0) + dx g(y0, x1)) + dy ((1 - dx) g(y1, x0) + dx g(y1, x1));
+ *   dst[c, i] = v(0, c) + v(1, c) + ... + v(side - 1, c), added in that order.
+ * All float64 for both element types: equal bit for bit to that sequence of IEEE operations evaluated anywhere.  This restates
+ * skimage.transform.radon(image, theta, circle=True) from its documentation (agreement with scikit-image itself: UNVERIFIED).
+ * The mem_kind / device / stream triple of dcp_label_2d; for DCP_MEM_DEVICE the call synchronises `stream` once (the table is copied
+ * from host memory).  A null pointer, side or nangles below 1, a stride below the side, an unknown dtype or mem_kind, src overlapping
+ * dst and a table entry that is not finite are DCP_ERR_INVALID_ARG; another dtype, side above 32768 and nangles above 65535 (so that
+ * every index fits 32 bits) are DCP_ERR_UNSUPPORTED; all before any device call. */
+int dcp_radon_2d(const void* src, double* dst, int side, long src_row_stride, int dtype, int nangles, const double* table, int mem_kind,
+                 int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the

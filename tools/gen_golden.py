@@ -897,7 +897,7 @@ def g27_tables():
     return tables
 
 
-def g27_images():
+def g27_images(with_g28=False):
     rng = np.random.default_rng(2728)
 
     def grid(shape, dist, deg, chess):
@@ -913,7 +913,10 @@ def g27_images():
             du, dv = (u + dist / 2) % dist - dist / 2, (v + dist / 2) % dist - dist / 2
             img = 1.0 - 0.8 * np.maximum(np.exp(-du * du / (2 * 1.6 ** 2)), np.exp(-dv * dv / (2 * 1.6 ** 2)))
         return (img * ramp * (1.0 + 0.01 * rng.standard_normal(shape))).astype(np.float32)
-    return dict(line=grid((160, 200), 20, 1.5, False), chess=grid((160, 200), 24, 1.5, True), tall=grid((300, 96), 20, 1.5, False))
+    images = dict(line=grid((160, 200), 20, 1.5, False), chess=grid((160, 200), 24, 1.5, True), tall=grid((300, 96), 20, 1.5, False))
+    if with_g28:             # (drawn after g27's three, which stay what they were)
+        images["big"] = grid((400, 420), 30, 3.2, False)
+    return images
 
 
 def g27():
@@ -1042,5 +1045,78 @@ def g27():
     assert os.path.getsize(os.path.join(OUT, "g27_cross_points.npz")) <= os.path.getsize(os.path.join(OUT, "g26_fourier_gauss.npz"))
 
 
+# ---- g28: the slope and distance search of prep.linepattern (calc_slope_distance_hor_lines / calc_slope_distance_ver_lines): what the
+# reference's own functions return with skimage stubbed as for g27 and skimage.transform.radon set to the NumPy restatement of its
+# documented definition (tests/helpers/radon_reference.py) -- scikit-image itself is not installed, so that link is UNVERIFIED.  Per case:
+# slope, distance, the relative gap between the two largest column maxima of the coarse and of the fine sinogram (no fixture may sit on a
+# tie), and e_dist: how far the reference's distance lies from the same computation with the closed-form sub-pixel parabola.
+def g28():
+    import json
+    import warnings
+    import discorpy.prep.linepattern as rlp                         # (imported, with its stubs, by g27)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import peaks_reference as pr
+    from helpers import radon_reference as rr
+    sinograms = []
+
+    def radon(image, theta=None, circle=True):
+        sinograms.append(rr.radon(image, theta=theta, circle=circle))
+        return sinograms[-1]
+    images = g27_images(with_g28=True)
+    line, big, chess = images["line"], images["big"], images["chess"]
+    out = dict(img_line=line, img_big=big, img_chess=chess)
+    small = dict(ratio=0.9, search_range=5, radius=5)
+    # (name, image, what is done to it, directions, arguments)
+    cases = [("line", "line", "", ("hor", "ver"), small),
+             ("big", "big", "", ("ver",), dict(ratio=0.5, search_range=10, radius=5)),
+             ("chess", "chess", "", ("hor", "ver"), dict(small, chessboard=True)),
+             ("dark", "line", "invert", ("hor", "ver"), dict(small, bgr="dark")),
+             ("float64", "line", "float64", ("hor", "ver"), small),
+             ("plain", "line", "", ("hor", "ver"), dict(small, denoise=False, norm=False, subpixel=False))]
+    names = []
+    polyfit = rlp.locate_subpixel_point
+
+    def closed_form(list_point, option="min"):
+        return pr.subpixel_offset(*list_point)
+    for name, key, prepare, directions, kw in cases:
+        mat = out["img_" + key]
+        if prepare == "invert":
+            mat = mat.max() - mat
+        if prepare == "float64":
+            mat = mat.astype(np.float64)
+        for direction in directions:
+            fn = rlp.calc_slope_distance_hor_lines if direction == "hor" else rlp.calc_slope_distance_ver_lines
+            del sinograms[:]
+            rlp.radon = radon
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    slope, dist = fn(mat, **kw)
+                    rlp.locate_subpixel_point = closed_form
+                    slope_closed, dist_closed = fn(mat, **kw)
+            finally:
+                rlp.radon, rlp.locate_subpixel_point = None, polyfit
+            assert slope_closed == slope and len(sinograms) == 4
+            gaps = []
+            for sino in sinograms[:2]:
+                top = np.sort(np.amax(sino, axis=0))
+                gaps.append((top[-1] - top[-2]) / top[-1])
+            assert min(gaps) > 1e-9, (name, direction, gaps)
+            e_dist = abs(dist - dist_closed)
+            assert np.isfinite(dist) and e_dist < 1e-9 and (kw.get("subpixel", True) or e_dist == 0), (name, direction, dist, e_dist)
+            full = "%s_%s" % (name, direction)
+            names.append(full)
+            out["image_" + full], out["prepare_" + full], out["args_" + full] = np.array(key), np.array(prepare), np.array(json.dumps(kw, sort_keys=True))
+            out["slope_" + full], out["dist_" + full] = np.float64(slope), np.float64(dist)
+            out["gap1_" + full], out["gap2_" + full], out["e_dist_" + full] = np.float64(gaps[0]), np.float64(gaps[1]), np.float64(e_dist)
+            print("g28 %-12s slope %+.7f distance %.4f gaps %.3g %.3g e_dist %.3g" % (full, slope, dist, gaps[0], gaps[1], e_dist))
+    out["case_names"] = np.array(names)
+    # the generator's own lines: 1.5 degree (line, chess) and 3.2 degree (big), recovered to the 0.05 degree grid of the fine search
+    assert abs(out["slope_line_hor"] - np.tan(np.deg2rad(1.5))) < 1e-3 and abs(out["slope_big_ver"] + np.tan(np.deg2rad(3.2))) < 1e-3
+    save("g28_slope_distance", **out)
+    assert os.path.getsize(os.path.join(OUT, "g28_slope_distance.npz")) <= 1 << 20
+
+
 g27()
+g28()
 print("done")

@@ -38,6 +38,20 @@ search (tests/helpers/peaks_reference.py: the reference's loop with the sort of 
 profiles, on this machine's CPU, and its positions are compared with the kernel's.
 
     python tools/time_gaussian.py --cross-points [--shape 1800x2000] [--dist 90] [--rounds 5] [--reps 5] [--no-numpy]
+
+--radon: the transform in front of that route, with options of its own.  Time the Radon transform (prep.linepattern.radon's call,
+dcp_radon_2d: one launch of radon_kernel for all angles) on device-resident planes: 600 x 600 float32 and float64 (the ROI of a
+2000-wide image at the default ratio of the slope search) x 61 angles, the coarse grid of calc_slope_distance_ver_lines (around 0
+degree: neighbouring lanes read neighbouring elements) and of calc_slope_distance_hor_lines (around 90 degree: neighbouring lanes read
+neighbouring ROWS of the source).  Per element type: warm-up calls of both sweeps, then `--rounds` (at least five) rounds; a round times
+`--reps` back-to-back calls of the 0-degree sweep between device events, then the same of the 90-degree sweep.  A call copies its angle
+table from host memory and waits for that copy before it enqueues the kernel, so a call is more than its kernel: the same call on a
+1 x 1 plane (a kernel of one thread and one row per angle) is timed beside it as the floor of a call.  Printed in ms per call: the
+median round of each sweep with its range, the floor, the ratio 90 / 0 of the calls and of the calls less the floor, and whether two
+calls of a sweep give the same bits.  There is no time to beat: the numbers go to DESIGN.md as they are; the ratio decides whether a
+patch of the source staged in LDS is worth its code.
+
+    python tools/time_gaussian.py --radon [--side 600] [--angles 61] [--dtypes float32,float64] [--rounds 5] [--reps 200]
 """
 import argparse
 import os
@@ -57,6 +71,8 @@ def main():
         return fourier_main([v for v in sys.argv[1:] if v != "--fourier"])
     if "--cross-points" in sys.argv[1:]:
         return cross_points_main([v for v in sys.argv[1:] if v != "--cross-points"])
+    if "--radon" in sys.argv[1:]:
+        return radon_main([v for v in sys.argv[1:] if v != "--radon"])
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
     ap.add_argument("--dtypes", default="float32,uint16")
@@ -326,6 +342,79 @@ def cross_points_main(argv):
         print("%-74s %9.1f ms (once; %d points, equal to the kernel's: %s)" % ("NumPy restatement of the peak search on this machine's CPU", cpu_ms,
                                                                                sum(len(r) for r in restated), same), flush=True)
     print("[%s]" % kernels, flush=True)
+
+
+def radon_main(argv):
+    ap = argparse.ArgumentParser(prog="time_gaussian.py --radon", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--side", type=int, default=600)
+    ap.add_argument("--angles", type=int, default=61)
+    ap.add_argument("--dtypes", default="float32,float64")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args(argv)
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    from discorpy_amd import _ffi as F
+    from discorpy_amd.prep.linepattern import _make_circle_mask, _radon_table
+    L = F.lib()
+    F.require_device()
+    dev, side, nang = -1, a.side, a.angles
+    dptr = F.C.POINTER(F.C.c_double)
+    rng = np.random.default_rng(11)
+    half = (nang - 1) / 2.0
+    sweeps = {"0": np.arange(-half, half + 1.0), "90": 90.0 + np.arange(-half, half + 1.0)}
+    # a line-pattern-like ROI under the mask of the slope search: lines 30 apart, noise, zero outside the circle
+    y, x = np.mgrid[0:side, 0:side]
+    roi = (1.0 + np.cos(2 * np.pi * (x + 0.03 * y) / 30.0) + 0.05 * rng.standard_normal((side, side))) * _make_circle_mask(side, 0.92)
+    print("radon: %d x %d plane, %d angles per call, %d rounds of %d calls, ms per call" % (side, side, nang, a.rounds, a.reps))
+    for name in a.dtypes.split(","):
+        dt = np.dtype(name)
+        code = F.DTYPE_BY_NAME[dt.name]
+        img = roi.astype(dt)
+        src = F.DeviceBuffer(img.nbytes, dev).upload(img)
+        dst = F.DeviceBuffer(side * nang * 8, dev)
+        tables = {k: _radon_table(v, side) for k, v in sweeps.items()}
+        floor_table = _radon_table(sweeps["0"], 1)
+
+        def run(key):
+            if key == "floor":
+                F.check(L.dcp_radon_2d(src.ptr, dst.ptr, 1, 1, code, nang, floor_table.ctypes.data_as(dptr), F.MEM_DEVICE, dev, None))
+            else:
+                F.check(L.dcp_radon_2d(src.ptr, dst.ptr, side, side, code, nang, tables[key].ctypes.data_as(dptr), F.MEM_DEVICE, dev, None))
+
+        def timed(key):
+            e0, e1 = F.Event(dev), F.Event(dev)
+            e0.record()
+            for _r in range(a.reps):
+                run(key)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_ms(e1) / a.reps
+        same = {}
+        for key in ("0", "90"):
+            for _ in range(a.warmup):
+                run(key)
+            first = dst.download((side, nang), np.float64)
+            run(key)
+            same[key] = np.array_equal(first, dst.download((side, nang), np.float64), equal_nan=True)
+        for _ in range(a.warmup):
+            run("floor")
+        kernel = F.last_kernel()
+        F.check(L.dcp_stream_synchronize(dev, None))
+        rounds = {"0": [], "90": [], "floor": []}
+        for _ in range(a.rounds):
+            for key in ("0", "90", "floor"):
+                rounds[key].append(timed(key))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        for key in ("0", "90"):
+            print("%-8s around %2s degree  %8.4f ms (rounds %.4f .. %.4f)  less the floor %8.4f ms  two calls equal: %s" % (
+                dt.name, key, med[key], min(rounds[key]), max(rounds[key]), med[key] - med["floor"], same[key]), flush=True)
+        print("%-8s floor of a call    %8.4f ms (rounds %.4f .. %.4f)  [1 x 1 plane, %d angles: the table's copy, the wait for it, one launch]" % (
+            dt.name, med["floor"], min(rounds["floor"]), max(rounds["floor"]), nang))
+        print("%-8s ratio 90 / 0       %8.3f of the calls, %.3f less the floor  [%s]" % (
+            dt.name, med["90"] / med["0"], (med["90"] - med["floor"]) / (med["0"] - med["floor"]), kernel), flush=True)
+    return 0
 
 
 if __name__ == "__main__":
