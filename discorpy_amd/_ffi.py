@@ -121,6 +121,9 @@ SIGNATURES = {
     "dcp_tilted_profiles_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       _int, _int, _vp]),
     "dcp_radon_2d": (_int, [_vp, _vp, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
+    "dcp_radon_padded_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
+    "dcp_nearest_sq_dists": (_int, [_vp, _vp, _int, _int, _int, _vp]),
+    "dcp_box_moments_2d": (_int, [_vp, _int, _int, C.c_long, _int, _vp, _int, _vp, _int, _int, _vp]),
     "dcp_label_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, C.POINTER(_int), _int, _int, _vp]),
     "dcp_label_measures_2d": (_int, [_vp, _vp, _int, _int, C.c_long, C.c_long, _int, _int, _vp, _vp, _int, _int, _vp]),
     "dcp_fill_holes_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),

@@ -331,6 +331,26 @@ constexpr int kRadonMaxAngles = 65535;         // one angle per blockIdx.y
 inline size_t radon_work_bytes(int nangles) { return (size_t)nangles * 4 * sizeof(double); }
 hipError_t launch_radon(const void* src, double* dst, int N, int64_t src_stride, int dtype, int nangles, const double* table, void* work,
                         hipStream_t stream);
+// dotgrid_kernels.hip, DESIGN.md ("Dot grid").  The sinogram of the H x W plane at src (kF32 / kF64, rows `src_stride` elements apart)
+// embedded in a square of zeros of side S = radon_padded_side(H, W) with its first element at (S / 2 - H / 2, S / 2 - W / 2): the square
+// transformed as launch_radon transforms its plane but without the circle; no padded plane exists, and nothing outside the H x W view is
+// read.  table: HOST array of {cos a, sin a, tx, ty} per angle FOR SIDE S.  dst: dense (S, nangles) doubles.  `work`:
+// radon_work_bytes(nangles) of device memory.  THE STREAM IS SYNCHRONISED once, after the table has been copied.
+inline int radon_padded_side(int H, int W) { return (int)__builtin_ceil(__builtin_sqrt(2.0) * (double)(H > W ? H : W)); }
+hipError_t launch_radon_padded(const void* src, double* dst, int H, int W, int64_t src_stride, int dtype, int nangles, const double* table,
+                               void* work, hipStream_t stream);
+// dst[i][0..3] (dense (N, 4) doubles) = the four smallest of (y_i - y_j) * (y_i - y_j) + (x_i - x_j) * (x_i - x_j) over all j (j = i
+// included), ascending, +inf where N < 4; pts: dense (N, 2) doubles (y, x), device memory.  One launch.
+constexpr int kNearMaxPoints = 1 << 20;
+hipError_t launch_nearest_sq_dists(const double* pts, double* dst, int N, hipStream_t stream);
+// sums[n][6] = count, sum y, sum x, sum y y, sum x y, sum x x over the nonzero elements of src (kBool or an 8- / 16-bit integer type) inside
+// box b = boxes[b][4] = min y, max y, min x, max x (inclusive, INSIDE THE PLANE or empty: max < min), (y, x) relative to the box's corner.
+// boxes: HOST array; `work`: box_work_bytes(n) of device memory.  THE STREAM IS SYNCHRONISED once, after the boxes have been copied.
+constexpr int kBoxMaxSide = 32768;             // every sum stays below 2^60
+constexpr int kBoxMaxBoxes = 1 << 24;
+inline size_t box_work_bytes(int n) { return (size_t)n * 4 * sizeof(int32_t); }
+hipError_t launch_box_moments(const void* src, int H, int W, int64_t src_stride, int dtype, const int32_t* boxes, int n, long long* sums,
+                              void* work, hipStream_t stream);
 // label_kernels.hip: connected components of the nonzero pixels (any ElemType; floats by their bits: NaN is set, -0.0 is not) numbered
 // as scipy.ndimage.label numbers them, into dst (dense H x W int32, 0 = background).  conn8: the full 3 x 3 structure, else the cross.
 // `parent`: H W int32 of device scratch, `counts`: label_count_words(H, W) more; the number of labels is left in the LAST word of

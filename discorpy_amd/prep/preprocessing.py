@@ -17,8 +17,11 @@
   ``scipy.ndimage.grey_opening`` with the 3 x 3 cross.  Results equal those composites element for element; scikit-image itself is
   not installed where this was written, so the link to it is by construction and UNVERIFIED ("Binarization")
 
-The rest of the reference's module (``regionprops`` behind ``select_dots_based_ratio``, the Radon-based angle search) rests on
-scikit-image and is out of scope here: there is nothing to compare an implementation against.
+The rest of the reference's module that rests on scikit-image (``regionprops`` behind ``select_dots_based_ratio``, the
+Radon-based angle search of ``calc_hor_slope`` / ``calc_ver_slope``) is restated from the documentation in :mod:`discorpy_amd.prep.dotpattern`, with
+``calc_size_distance`` and the grouping of the dots into lines, and imported here (``DOT_GRID``, at the bottom); scikit-image itself stays
+out of scope: it is not installed where this was written, so those links are by construction and UNVERIFIED.  Not here:
+``calculate_threshold``, the parabola masks, ``rotate_points``, ``remove_subset_points`` and the polyfit-based grouping.
 
 The median runs as a hand-written HIP kernel through ``dcp_median_filter_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/median_kernels.hip``): it SELECTS the element of rank ``(size_y * size_x) // 2`` of every window by a binary search on
@@ -87,6 +90,9 @@ FOURIER = ["normalization_fft", "_apply_fft_filter", "_make_window", "_fourier_t
 BINARIZATION = ["threshold_otsu", "clear_border", "opening", "binarization"]
 DOT_PATTERN = ["label", "sum_labels", "center_of_mass", "find_objects", "binary_fill_holes", "check_num_dots", "get_points_dot_pattern",
                "select_dots_based_size", "select_dots_based_distance"]
+# the rest of that route, from prep.dotpattern (imported at the bottom of this module)
+DOT_GRID = ["radon_padded", "calc_size_distance", "select_dots_based_ratio", "calc_hor_slope", "calc_ver_slope", "group_dots_hor_lines",
+            "group_dots_ver_lines", "remove_residual_dots_hor", "remove_residual_dots_ver"]
 
 
 def _window(size):
@@ -738,17 +744,20 @@ def select_dots_based_distance(mat, dot_dist, ratio=0.3):
     Keep the dots one of whose three nearest neighbours lies within ``ratio`` (as a fraction of ``dot_dist``) above a whole multiple
     of ``dot_dist`` (reference ``preprocessing.py:422-457``).
 
-    Returns an int16 NumPy array (also for a tensor).  Labels, boxes and centroids come from the GPU; the distances between the
-    centroids and the per-box copy are NumPy, in the reference's operation order.
+    Returns an int16 NumPy array (also for a tensor).  Labels, boxes and centroids come from the GPU, and so do the squared distances
+    from every centroid to its nearest ones (``dcp_nearest_sq_dists``: the operations NumPy performs for the reference's expression,
+    so the same bits); their root, the test and the per-box copy are NumPy.  A centroid that is not finite raises ``ValueError``.
     """
+    from .dotpattern import _nearest_sq
     mat = np.int16(_host_array(mat))
     labels, num_dots = label(mat)
     sums, boxes = _measures(mat, labels, num_dots, top=num_dots)          # boxes and centroids from one launch
     boxes = _slices(boxes, num_dots)
     cents = np.asarray(_centroids(sums, np.arange(1, num_dots + 1)))
     kept = np.zeros_like(mat)
+    nearest = np.sqrt(_nearest_sq(cents))[:, 1:min(4, num_dots)]          # (the sorted row's [1:4]; fewer dots, fewer entries)
     for i, box in enumerate(boxes):
-        dist = np.sort(np.sqrt((cents[i][0] - cents[:, 0]) ** 2 + (cents[i][1] - cents[:, 1]) ** 2))[1:4]
+        dist = nearest[i]
         dist_error = (dist - (dist // dot_dist) * dot_dist) / dot_dist
         if any(dist_error < ratio):
             kept[box] = mat[box]
@@ -1099,3 +1108,9 @@ def binarization(mat, ratio=0.3, thres=None, denoise=True):
         return filled.to(torch.int16)
     F.check(F.lib().dcp_stream_synchronize(img.device, img.stream))
     return np.int16(filled.copy_to_host())
+
+
+# --------------------------------------------------------------------------- the rest of the dot-pattern route (prep.dotpattern)
+
+from .dotpattern import (radon_padded, calc_size_distance, select_dots_based_ratio, calc_hor_slope, calc_ver_slope,  # noqa: E402,F401
+                         group_dots_hor_lines, group_dots_ver_lines, remove_residual_dots_hor, remove_residual_dots_ver)

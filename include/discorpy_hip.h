@@ -667,6 +667,37 @@ int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, lo
 int dcp_radon_2d(const void* src, double* dst, int side, long src_row_stride, int dtype, int nangles, const double* table, int mem_kind,
                  int device, void* stream);
 
+/* ---- the dot-grid route (discorpy/prep/preprocessing.py:274-558: calc_size_distance, select_dots_based_ratio, calc_hor_slope,
+ * calc_ver_slope) ----
+ * dcp_radon_padded_2d: the sinogram of a height x width plane (FLOAT32 / FLOAT64, rows `src_row_stride` elements apart, read in place)
+ * embedded in a square of zeros: S = (int)ceil(sqrt(2.0) * max(height, width)) in double, the plane's first element at
+ * (S / 2 - height / 2, S / 2 - width / 2) (integer divisions).  That square is transformed as dcp_radon_2d transforms a plane of side S
+ * -- the same table {ca, sa, tx, ty} per angle MADE FOR SIDE S, the same samples, weights and ascending row sum -- but WITHOUT the
+ * circle: g(y, x) is 0.0 exactly where (y, x) lies outside the plane's rectangle and the element, a NaN included, everywhere inside.
+ * No padded plane is made and nothing outside the height x width view is read.  dst: (S, nangles) doubles, row-major.  This restates
+ * skimage.transform.radon(image, theta, circle=False) from its documentation (agreement with scikit-image itself: UNVERIFIED).
+ * Refusals as for dcp_radon_2d, with S (at most 32768, so max(height, width) <= 23170) in the place of its side.
+ *
+ * dcp_nearest_sq_dists: for `npoints` points (y, x) -- dense (npoints, 2) doubles -- dst[i][0..3] = the four smallest of
+ *   (y_i - y_j) * (y_i - y_j) + (x_i - x_j) * (x_i - x_j)     (two differences, two products, one sum, each rounded; no fused multiply-add)
+ * over ALL j, j = i included, in ascending order; +inf where npoints < 4.  dst: dense (npoints, 4) doubles where the points live.  SQUARED
+ * distances: the caller takes the root.  One launch.  1 <= npoints <= 2^20.  Coordinates must be finite: host memory is checked
+ * (DCP_ERR_INVALID_ARG), device memory is the caller's word.
+ *
+ * dcp_box_moments_2d: per box b of `boxes` (HOST array of nboxes x {min y, max y, min x, max x}, inclusive, as dcp_label_measures_2d writes
+ * them), sums[b][0..5] = count, sum y, sum x, sum y y, sum x y, sum x x over EVERY nonzero element of the plane inside the box -- whatever
+ * label it carries -- each weighing 1, with (y, x) relative to the box's corner.  The plane: BOOL or an 8- / 16-bit integer type, sides at
+ * most 32768 (every sum then stays below 2^60).  An empty box (max < min) gives zeros; a box that is not empty and reaches outside the
+ * plane is DCP_ERR_INVALID_ARG.  sums: dense (nboxes, 6) int64 where the plane lives.  nboxes = 0 returns at once.  For DCP_MEM_DEVICE
+ * the call synchronises `stream` once (the boxes are copied from host memory).
+ * All three: the mem_kind / device / stream triple of dcp_label_2d; null pointers, sizes below 1, a stride below the width, an unknown
+ * dtype or mem_kind and an output that overlaps the source are DCP_ERR_INVALID_ARG; all before any device call. */
+int dcp_radon_padded_2d(const void* src, double* dst, int height, int width, long src_row_stride, int dtype, int nangles, const double* table,
+                        int mem_kind, int device, void* stream);
+int dcp_nearest_sq_dists(const double* points, double* dst, int npoints, int mem_kind, int device, void* stream);
+int dcp_box_moments_2d(const void* src, int height, int width, long src_row_stride, int dtype, const int32_t* boxes, int nboxes, int64_t* sums,
+                       int mem_kind, int device, void* stream);
+
 /* discorpy/post/postprocessing.py:36-64 (unwarp_line_forward) and discorpy/util/utility.py:192-230
  * (find_point_to_point): the radial model applied to npts points given as (y, x) pairs of doubles,
  * out = centre + B(r) * (p - centre) with B(r) = sum_i list_fact[i] * r^i.  Float64; agrees with the

@@ -1117,6 +1117,177 @@ def g28():
     assert os.path.getsize(os.path.join(OUT, "g28_slope_distance.npz")) <= 1 << 20
 
 
+# ---- g29: the dot-grid route of prep.dotpattern (calc_size_distance, select_dots_based_ratio / _distance, calc_hor_slope / calc_ver_slope,
+# the grouping and the residual filter): what the reference's own functions return with skimage stubbed as for g28 -- radon <- the padded
+# restatement (tests/helpers/radon_padded_reference.py), clear_border <- binarize_reference.clear_border, regionprops <- the moments
+# helper (tests/helpers/regionprops_reference.py); scikit-image itself is not installed, so those links are UNVERIFIED.  Per case: the
+# relative gap between the two largest column maxima of each sinogram and the least |val - ratio| / ratio over the dots (no fixture may
+# sit on a tie or on the threshold).
+def g29_images():
+    def grid(shape, pitch, radius, deg, k):
+        h, w = shape
+        img = np.zeros(shape, np.uint8)
+        y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+        t = np.deg2rad(deg)
+        n = max(h, w) // pitch + 2
+        for i in range(-n, n + 1):
+            for j in range(-n, n + 1):
+                u, v = j * pitch * np.cos(t) - i * pitch * np.sin(t), j * pitch * np.sin(t) + i * pitch * np.cos(t)
+                s = 1.0 + k * (u * u + v * v)                  # a mild radial term
+                cy, cx = h / 2 + 0.3 + s * v, w / 2 - 0.4 + s * u
+                if radius + 3 <= cy < h - radius - 3 and radius + 3 <= cx < w - radius - 3:
+                    img[(y - cy) ** 2 + (x - cx) ** 2 <= radius * radius] = 1
+        return img
+
+    def spoil(img, pitch, radius, dropped):
+        h, w = img.shape
+        labels, num = ndi.label(img)
+        cents = np.asarray(ndi.center_of_mass(img, labels, np.arange(1, num + 1)))
+        boxes = ndi.find_objects(labels)
+        mid = np.array([h / 2, w / 2])
+        order = np.argsort(((cents - mid) ** 2).sum(1))
+        y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+
+        def ellipse(cy, cx, a, b):
+            return ((y - cy) / b) ** 2 + ((x - cx) / a) ** 2 <= 1.0
+        marks = {}                                              # a pixel of each spoiled item
+        # two merged dots: a dot and its neighbour to the right (away from the middle: the slope search starts at the dot nearest the mean)
+        c0 = cents[order[24]]
+        right = min((i for i in range(num) if cents[i][1] > c0[1] + pitch / 2), key=lambda i: ((cents[i] - c0) ** 2).sum())
+        yy = int(round((c0[0] + cents[right][0]) / 2))
+        img[yy - 1:yy + 2, int(c0[1]):int(cents[right][1]) + 1] = 1
+        marks["merged"] = (yy, int(c0[1]))
+        # an ellipse at axis ratio 1.25 (kept) and one at `dropped` (1.4; 1.6 at radius 4, where the pixels of 1.25 and 1.4 are the same)
+        for pos, axis_ratio, mark in ((order[5], 1.25, "ellipse_kept"), (order[6], dropped, "ellipse_dropped")):
+            img[boxes[pos]] = 0
+            img[ellipse(cents[pos][0], cents[pos][1], radius * np.sqrt(axis_ratio), radius / np.sqrt(axis_ratio))] = 1
+            marks[mark] = (int(round(cents[pos][0])), int(round(cents[pos][1])))
+        # a dot whose box contains part of a neighbour: a 2 x 2 block with one pixel in the corner of the box
+        pos = order[9]
+        by, bx = boxes[pos][0].start, boxes[pos][1].start
+        assert img[by, bx] == 0 and img[by + 1, bx] == 0 and img[by, bx + 1] == 0 and not img[by - 2:by + 1, bx - 2:bx + 1].any()
+        img[by - 1:by + 1, bx - 1:bx + 1] = 1
+        marks["neighbour"], marks["crowded_dot"] = (by, bx), (int(round(cents[pos][0])), int(round(cents[pos][1])))
+        # between four dots: a 1-pixel-high bar, a 2 x 2 block, a diagonal pixel pair
+        for pos, kind in ((order[30], "bar"), (order[40], "block"), (order[50], "pair")):
+            gy, gx = int(cents[pos][0] + pitch / 2), int(cents[pos][1] + pitch / 2)
+            assert not img[gy - 2:gy + 4, gx - 4:gx + 5].any(), kind
+            marks[kind] = (gy, gx)
+            if kind == "bar":
+                img[gy, gx - 2:gx + 3] = 1
+            elif kind == "block":
+                img[gy:gy + 2, gx:gx + 2] = 1
+            else:
+                img[gy, gx] = img[gy + 1, gx + 1] = 1
+        # a dot touching the border
+        gx = int(cents[order[0]][1] + pitch / 2)
+        img[ellipse(2.0, gx, radius, radius)] = 1
+        marks["border"] = (0, gx)
+        assert all(img[m] == 1 for m in marks.values())
+        assert ndi.label(img)[1] == num - 1 + 1 + 1 + 1 + 2 + 1       # merged, neighbour, bar, block, pair (two labels), border dot
+        return img, marks
+    return dict(a=spoil(grid((200, 260), 20, 4, 2.0, 2e-7), 20, 4, 1.6), b=spoil(grid((360, 300), 24, 5, -1.5, 1e-7), 24, 5, 1.4))
+
+
+def g29():
+    import types
+    import warnings
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    for mod, attr in (("skimage.filters", "threshold_otsu"), ("skimage.segmentation", "clear_border"), ("skimage.transform", "radon")):
+        if not hasattr(sys.modules[mod], attr):
+            setattr(sys.modules[mod], attr, None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import discorpy.prep.preprocessing as rprep
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import binarize_reference as br
+    import radon_padded_reference as rpr
+    import regionprops_reference as rgp
+    sinograms = []
+
+    def radon(image, theta=None, circle=True):
+        assert circle is False
+        sinograms.append(rpr.radon(image, theta=theta))
+        return sinograms[-1]
+    saved = rprep.radon, rprep.clear_border, getattr(rprep.meas, "regionprops", None)
+    rprep.radon, rprep.clear_border, rprep.meas.regionprops = radon, br.clear_border, rgp.regionprops
+    select_ratio = 0.3
+    out, names = {}, []
+
+    def lines_out(key, lines):
+        out[key + "_pts"] = f64(np.concatenate(lines))
+        out[key + "_len"] = np.array([len(line) for line in lines], np.int64)
+    try:
+        for key, (img, marks) in g29_images().items():
+            out["img_" + key] = img
+            out["mark_names_" + key], out["marks_" + key] = np.array(sorted(marks)), np.array([marks[m] for m in sorted(marks)], np.int64)
+            mat = np.int16(img)
+            # the least |val - ratio| / ratio over the dots the reference measures (boxes of at least 2 x 2)
+            labels, num = ndi.label(mat)
+            margins, vals = [], []
+            for box in ndi.find_objects(labels):
+                sub = mat[box]
+                if min(sub.shape) >= 2:
+                    major, minor = rgp.axis_lengths(sub)
+                    assert minor > 0
+                    vals.append(abs(major / minor - 1.0))
+                    margins.append(abs(vals[-1] - select_ratio) / select_ratio)
+            assert min(margins) > 1e-6, (key, min(margins))
+            kept_ratio = rprep.select_dots_based_ratio(mat, select_ratio)
+            want = dict(merged=0, ellipse_kept=1, ellipse_dropped=0, neighbour=1, crowded_dot=1, bar=0, block=1, pair=0)
+            assert all(kept_ratio[marks[m]] == v for m, v in want.items()), {m: int(kept_ratio[marks[m]]) for m in want}
+            for roi in (0.9, 0.6):
+                name = "%s_%d" % (key, round(roi * 100))
+                del sinograms[:]
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    size, dist = rprep.calc_size_distance(mat, roi)
+                    slope_hor = rprep.calc_hor_slope(mat, roi)
+                    slope_ver = rprep.calc_ver_slope(mat, roi)
+                assert len(sinograms) == 2
+                gaps = []
+                for sino in sinograms:
+                    top = np.sort(np.amax(sino, axis=0))
+                    gaps.append((top[-1] - top[-2]) / top[-1])
+                assert min(gaps) > 1e-9, (name, gaps)
+                kept_size = rprep.select_dots_based_size(mat, size)
+                kept_dist = rprep.select_dots_based_distance(mat, dist)
+                # the flow of the reference's example_01: size, ratio, then the lines
+                mat1 = rprep.select_dots_based_ratio(kept_size, select_ratio)
+                hor = rprep.group_dots_hor_lines(mat1, slope_hor, dist)
+                ver = rprep.group_dots_ver_lines(mat1, slope_ver, dist)
+                hor2 = rprep.remove_residual_dots_hor(hor, slope_hor)
+                ver2 = rprep.remove_residual_dots_ver(ver, slope_ver)
+                lab1, num1 = ndi.label(mat1)
+                points = f64(ndi.center_of_mass(mat1, lab1, np.arange(1, num1 + 1)))
+                for a, b in zip(hor + ver, rprep.group_dots_hor_lines(points, slope_hor, dist) + rprep.group_dots_ver_lines(points, slope_ver, dist)):
+                    assert np.array_equal(a, b)          # (the point-list path: the same lines)
+                names.append(name)
+                out["roi_" + name], out["size_" + name], out["dist_" + name] = np.float64(roi), np.float64(size), np.float64(dist)
+                out["slope_hor_" + name], out["slope_ver_" + name] = np.float64(slope_hor), np.float64(slope_ver)
+                out["gap_hor_" + name], out["gap_ver_" + name] = np.float64(gaps[0]), np.float64(gaps[1])
+                out["kept_size_" + name], out["kept_dist_" + name] = kept_size.astype(np.uint8), kept_dist.astype(np.uint8)
+                out["flow_" + name], out["points_" + name] = mat1.astype(np.uint8), points
+                lines_out("hor_" + name, hor)
+                lines_out("ver_" + name, ver)
+                lines_out("hor2_" + name, hor2)
+                lines_out("ver2_" + name, ver2)
+                print("g29 %-5s size %.1f dist %.4f slopes %+.6f %+.6f gaps %.3g %.3g lines %d / %d margin %.3g"
+                      % (name, size, dist, slope_hor, slope_ver, gaps[0], gaps[1], len(hor), len(ver), min(margins)))
+            out["kept_ratio_" + key] = kept_ratio.astype(np.uint8)
+            out["margin_" + key], out["vals_" + key] = np.float64(min(margins)), f64(vals)
+    finally:
+        rprep.radon, rprep.clear_border, rprep.meas.regionprops = saved
+    out["case_names"], out["select_ratio"] = np.array(names), np.float64(select_ratio)
+    # the generator's own grids: 2.0 and -1.5 degree
+    assert abs(out["slope_hor_a_90"] - np.tan(np.deg2rad(2.0))) < 2e-3 and abs(out["slope_ver_a_90"] + np.tan(np.deg2rad(2.0))) < 2e-3
+    assert abs(out["slope_hor_b_90"] + np.tan(np.deg2rad(1.5))) < 2e-3
+    save("g29_dot_grid", **out)
+    assert os.path.getsize(os.path.join(OUT, "g29_dot_grid.npz")) <= 1 << 20
+
+
 g27()
 g28()
+g29()
 print("done")

@@ -14,6 +14,19 @@ labels.  scipy is timed at the `--scipy-side` (2048) only, once per case, and th
 whether scipy's output equals the GPU's.  The last line is the core clock and package power under the 4096^2 uint8 label call.
 
     python tools/time_label.py [--sides 2048,4096] [--dtypes uint8,float32] [--rounds 5] [--reps 3] [--no-scipy]
+
+With `--dotgrid` it times the kernels that follow the labelling in the dot-pattern route instead (discorpy_amd.prep.dotpattern;
+csrc/dotgrid_kernels.hip), in ms per call: warm-up calls, then `--rounds` rounds of back-to-back calls that end synchronised, the median
+round and the rounds' minimum and maximum; where two routes are compared they alternate round by round in one process.
+
+  * the nearest squared distances (dcp_nearest_sq_dists, host points in and out) against the NumPy loop it replaces -- per point
+    ``np.sort(np.sqrt(...))[1:4]`` over all points -- at `--points` (400, 2 000 and 10 000), with whether the results are equal;
+  * radon_padded against linepattern.radon on the same device-resident 600 x 600 float32 ROI x 61 angles: the padded one has sqrt(2)
+    times the columns and sqrt(2) times the rows, so twice the samples; the ratio is printed;
+  * whole calc_size_distance and calc_hor_slope on a `--grid-side` (2048) square dot grid (radius 8, pitch 40, rotated by 1.5 degree)
+    from a tensor.
+
+    python tools/time_label.py --dotgrid [--rounds 5] [--dotgrid-reps 10] [--points 400,2000,10000] [--grid-side 2048]
 """
 import argparse
 import os
@@ -30,6 +43,70 @@ def dot_grid(side, radius=8, pitch=40):
     return ((y % pitch - pitch // 2) ** 2 + (x % pitch - pitch // 2) ** 2 <= radius * radius)
 
 
+def rotated_dot_grid(side, radius=8, pitch=40, deg=1.5):
+    y, x = np.mgrid[0:side, 0:side].astype(np.float64)
+    t = np.deg2rad(deg)
+    u, v = x * np.cos(t) + y * np.sin(t) + 7.3, -x * np.sin(t) + y * np.cos(t) + 11.9
+    du, dv = (u + pitch / 2) % pitch - pitch / 2, (v + pitch / 2) % pitch - pitch / 2
+    return (du * du + dv * dv <= radius * radius).astype(np.int16)
+
+
+def nearest_numpy_loop(cents):
+    return np.asarray([np.sort(np.sqrt((dot[0] - cents[:, 0]) ** 2 + (dot[1] - cents[:, 1]) ** 2))[1:4] for dot in cents])
+
+
+def dotgrid(a):
+    """The --dotgrid mode (module docstring)."""
+    import torch
+    from discorpy_amd import _ffi as F
+    from discorpy_amd.prep import dotpattern as dp
+    from discorpy_amd.prep import linepattern as lp
+    F.require_device()
+
+    def sync():
+        torch.cuda.synchronize()
+
+    def alternated(routes, reps):
+        """{name: ms per call of every round} of the routes (name -> callable), alternated round by round."""
+        got = {name: [] for name in routes}
+        for fn in routes.values():
+            for _ in range(a.warmup + 1):
+                fn()
+        sync()
+        for _ in range(a.rounds):
+            for name, fn in routes.items():
+                t0 = time.perf_counter()
+                for _r in range(reps):
+                    fn()
+                sync()
+                got[name].append((time.perf_counter() - t0) * 1e3 / reps)
+        return got
+
+    def line(label, r):
+        print("%-58s %10.4f ms  (rounds %.4f .. %.4f)" % (label, float(np.median(r)), min(r), max(r)), flush=True)
+        return float(np.median(r))
+
+    rng = np.random.default_rng(11)
+    for n in [int(v) for v in a.points.split(",")]:
+        side = int(np.ceil(np.sqrt(n)))
+        cents = (np.stack(np.divmod(np.arange(n), side), axis=1) * 40.0 + rng.random((n, 2)) * 6.0).astype(np.float64)
+        got = alternated({"gpu": lambda: np.sqrt(dp._nearest_sq(cents))[:, 1:4], "numpy": lambda: nearest_numpy_loop(cents)}, 1 if n > 2000 else 3)
+        g = line("nearest distances, N = %d: dcp_nearest_sq_dists + sqrt" % n, got["gpu"])
+        c = line("nearest distances, N = %d: the NumPy loop" % n, got["numpy"])
+        print("    ratio %.1f, equal: %s" % (c / g, np.array_equal(np.sqrt(dp._nearest_sq(cents))[:, 1:4], nearest_numpy_loop(cents))), flush=True)
+    roi = torch.from_numpy(rng.random((600, 600)).astype(np.float32)).to("cuda:0")
+    theta = 90.0 + np.arange(-30.0, 31.0)
+    got = alternated({"padded": lambda: dp.radon_padded(roi, theta), "circle": lambda: lp.radon(roi, theta)}, a.dotgrid_reps)
+    p = line("radon_padded, 600 x 600 float32 x 61 angles (side %d)" % dp._padded_side(600, 600), got["padded"])
+    c = line("radon (circle), the same ROI", got["circle"])
+    print("    ratio padded / circle %.2f (twice the samples)" % (p / c), flush=True)
+    grid = torch.from_numpy(rotated_dot_grid(a.grid_side)).to("cuda:0")
+    got = alternated({"size": lambda: dp.calc_size_distance(grid), "slope": lambda: dp.calc_hor_slope(grid)}, max(a.dotgrid_reps // 2, 1))
+    line("calc_size_distance, %d x %d int16 tensor" % (a.grid_side, a.grid_side), got["size"])
+    line("calc_hor_slope, %d x %d int16 tensor" % (a.grid_side, a.grid_side), got["slope"])
+    print("    size, distance %r; slope %r" % (dp.calc_size_distance(grid), dp.calc_hor_slope(grid)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
@@ -39,9 +116,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--scipy-side", type=int, default=2048, help="the side at which scipy is timed and compared (0 or --no-scipy: never)")
     ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--dotgrid", action="store_true", help="time the dot-grid kernels instead (the last part of the description)")
+    ap.add_argument("--dotgrid-reps", type=int, default=10)
+    ap.add_argument("--points", default="400,2000,10000")
+    ap.add_argument("--grid-side", type=int, default=2048)
     a = ap.parse_args()
     if a.rounds < 5:
         ap.error("--rounds must be at least 5")
+    if a.dotgrid:
+        return dotgrid(a)
     import bench
     from discorpy_amd import _ffi as F
     L = F.lib()
