@@ -7,26 +7,23 @@
 //
 // The coefficient planes come from the single-plane prefilter, run once per channel on the column-strided view of that channel
 // (launch_spline_prefilter), so plane c holds bit for bit what the single-plane call on mat[:, :, c] filters.  The gathers keep
-// spline_wg_kernel's staging decision and its per-pixel arithmetic (spline_device.h), so every channel of the result is bit for
-// bit what the single-plane entry point returns for that channel -- under scipy's tap order and under the factorised sum.
+// spline_wg_kernel's staging decision (sw_box, spline_gather.h) and its per-pixel arithmetic (spline_device.h), so every channel of
+// the result is bit for bit what the single-plane entry point returns for that channel -- under scipy's tap order and under the
+// factorised sum.
+//
+// Shared with the other two gather files through spline_gather.h: corner hull, box rule and `staged`; the fill's extent and first
+// chunk; the row table; the launch grids, dispatch and kernel name.  Written out here as in spline_kernels.hip, which holds the commented
+// copy: the tile order, issue_fill with its masked last load, the tap sum out of the slab, the folding gather (why: spline_gather.h).
 //
 // Staged kernel: the tile's corner hull, box and `staged` test are evaluated once; phase 1 (row table, map_coord, round_clip_f32)
-// runs once; then per channel the slab is refilled from that channel's plane by LDS-DMA and phase 2 reads it.  Between channels:
-//   RAW  the wave's own loads are retired (vmcnt(0)), then a barrier, then the first read of the slab;
-//   WAR  the wave's reads of the slab are retired (lgkmcnt(0)), then a barrier, then the next channel's first load.
+// runs once; then per channel the slab is refilled from that channel's plane by LDS-DMA and phase 2 reads it.  Between channels the
+// RAW / WAR discipline told in spline_gather.h (the slab's fill).
 // Bound: per channel as spline_wg_kernel (LDS reads and float64 VALU); the coordinate chain -- about 20 of the 70 (order 3) to 120
 // (order 5) instructions per pixel and plane -- is paid once.  No MFMA: a gather, not a contraction.
-#include "dcp_internal.h"
-#include "dcp_device.h"
+#include "spline_gather.h"
 #include "dcp_pixel_store.h"
-#include "spline_device.h"
-#include <cstdio>
-#include <type_traits>
 
 namespace dcp {
-
-// (orders the wave's LDS traffic only: the reads of the slab are retired before the barrier that lets the next fill start)
-__device__ __forceinline__ void lds_reads_done_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Workgroups per CU the register allocation aims at.  spline_wg_kernel's: three below order 5 (the slab and the row tables fit three
 // times into a CU's LDS), two at order 5.  Next to one plane's working set a thread keeps its 16 NC float32 results until its pixels
@@ -63,39 +60,15 @@ __global__ void __launch_bounds__(256, (spline_color_wg_per_cu<ORDER, NC>())) sp
   const int y0 = __builtin_amdgcn_readfirstlane(ty * kSwTH + wy * 16);
   const int x = tx * kSwTW + wx * 64 + lane;
   const float wmaxf = (float)(a.W - 1), hmaxf = (float)(a.H - 1);
-  // ---- corner pixels (lanes 0..3) -> hull of their taps' base positions in the padded plane
-  int cx0, cx1, cy0, cy1;
-  {
-    const double X = (double)min(tx * kSwTW + (lane & 1) * (kSwTW - 1), a.W - 1);
-    const double Y = (double)min(ty * kSwTH + ((lane >> 1) & 1) * (kSwTH - 1), a.H - 1);
-    double xd, yd;
-    corner_coord<KIND, NF>(map, X, Y, &xd, &yd);
-    const int cxi = (int)round_clip_f32(xd, wmaxf) + a.pad, cyi = (int)round_clip_f32(yd, hmaxf) + a.pad;
-    const int xa = __builtin_amdgcn_readlane(cxi, 0), xb = __builtin_amdgcn_readlane(cxi, 1);
-    const int xc_ = __builtin_amdgcn_readlane(cxi, 2), xd_ = __builtin_amdgcn_readlane(cxi, 3);
-    const int ya = __builtin_amdgcn_readlane(cyi, 0), yb = __builtin_amdgcn_readlane(cyi, 1);
-    const int yc_ = __builtin_amdgcn_readlane(cyi, 2), yd_ = __builtin_amdgcn_readlane(cyi, 3);
-    cx0 = min(min(xa, xb), min(xc_, xd_));
-    cx1 = max(max(xa, xb), max(xc_, xd_));
-    cy0 = min(min(ya, yb), min(yc_, yd_));
-    cy1 = max(max(ya, yb), max(yc_, yd_));
-  }
-  // (the box rule of spline_wg_kernel: every tap of every pixel of the tile inside [c0 - 1 - ORDER/2, c1 + 2 + (ORDER + 1)/2])
-  const int bx0 = cx0 - 1 - ORDER / 2, bx1 = cx1 + 2 + (ORDER + 1) / 2;
-  const int by0 = cy0 - 1 - ORDER / 2, by1 = cy1 + 2 + (ORDER + 1) / 2;
-  const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-  // staged: the box fits the slab and lies inside the plane (no tap folds); workgroup-uniform, the same for every channel
-  const bool staged = bw <= kSwBoxW && bh <= kSwBoxH && bx0 >= 0 && by0 >= 0 && bx1 <= a.Wp - 1 && by1 <= a.Hp - 1;
-  // every plane gets its own descriptor, which ends with the box's last row (a chunk of a later row: zeros, no memory access)
-  const uint32_t rstep = (uint32_t)a.Wp * 8u;
-  const unsigned long long plane_bytes = (unsigned long long)a.Hp * rstep, rows_end = (unsigned long long)(by1 + 1) * rstep;
-  const uint32_t fill_extent = (uint32_t)(staged && rows_end < plane_bytes ? rows_end : plane_bytes);
+  // ---- corner hull -> box of every tap of the tile -> staged (spline_gather.h); the same for every channel
+  const SwBox box = sw_box<KIND, ORDER, NF>(a, map, tx, ty, lane);
+  const int bx0 = box.bx0, by0 = box.by0;
+  const bool staged = box.staged;
+  // the fill (spline_gather.h): every plane gets a descriptor of its own, which ends with the box's last row
+  const SwFill fill = sw_fill(a, box, wave, lane);
+  const uint32_t rstep = fill.rstep, fill_extent = fill.extent, off0 = fill.off0;
+  const int c160 = fill.c160, nchunk = fill.nchunk;
   const size_t plane_elems = (size_t)a.Hp * (size_t)a.Wp;
-  const int fc = wave * 64 + lane;
-  const int crow0 = fc / kSwCH;
-  const int c160 = fc - crow0 * kSwCH;
-  const uint32_t off0 = ((uint32_t)by0 * (uint32_t)a.Wp + (uint32_t)bx0) * 8u + (uint32_t)crow0 * rstep + (uint32_t)c160 * 16u;
-  const int nchunk = bh * kSwCH;
   auto issue_fill = [&](auto jc, const __amdgpu_buffer_rsrc_t src_rsrc, const uint32_t off0, const int c160) {
     constexpr int j = decltype(jc)::value;
     if constexpr (j < kSwNJ) {
@@ -117,12 +90,8 @@ __global__ void __launch_bounds__(256, (spline_color_wg_per_cu<ORDER, NC>())) sp
   auto plane_rsrc = [&](int c) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)(a.coef + (size_t)c * plane_elems), 0, (int)fill_extent, 0x00020000);
   };
-  // ---- row table of this wave's 16 rows (lanes 0..15; same-wave LDS traffic is ordered, no barrier)
-  if (lane < 16) fill_row<KIND, RW>(map, s_row[wave], lane, (double)min(y0 + lane, a.H - 1));
-  if constexpr (NF < 0 && KIND != kPersp) {
-    if ((int)threadIdx.x < map.nfact) s_coef[threadIdx.x] = map.fact[threadIdx.x];
-    __syncthreads();
-  }
+  // ---- row table of this wave's 16 rows, a long polynomial into LDS (spline_gather.h)
+  sw_stage_rows<KIND, NF, RW>(a, map, s_row, s_coef, wave, lane, y0);
   // ---- phase 1, once for all channels: the float32 coordinates of this wave's 16 rows, the loads of channel 0 going out between them
   const int rows = __builtin_amdgcn_readfirstlane(max(0, min(16, a.H - y0)));
   const ColCtx col = make_col<KIND, NF>(map, min(x, a.W - 1));
@@ -262,7 +231,7 @@ __global__ void __launch_bounds__(256, (spline_color_wg_per_cu<ORDER, NC>())) sp
           keep(c, k, value(k));
         }
       }
-      if (c + 1 < NC) lds_reads_done_barrier();            // every wave's reads of the slab are retired: the next fill may overwrite it
+      if (c + 1 < NC) lds_barrier();                       // every wave's reads of the slab are retired: the next fill may overwrite it
     }
   };
   // float32 results (the common case): the NC values of a pixel stay in registers and leave in one store of the pixel -- where the
@@ -351,58 +320,30 @@ __global__ void __launch_bounds__(kSplBlock) spline_remap_color_kernel(const Spl
 
 DCP_DEFINE_BOUNDS_READER(read_bounds_spline_color)
 
-template <int KIND, int NF, int NC>
-static hipError_t launch_wg_color_nc(const SplineArgs& a, const MapArgs& map, void* dst, hipStream_t stream) {
-  const unsigned tiles_x = (unsigned)((a.W + kSwTW - 1) / kSwTW);
-  const dim3 grid(a.xcd_remap ? ((tiles_x + 7u) / 8u) * 8u : tiles_x, (unsigned)((a.H + kSwTH - 1) / kSwTH));
-#define DCP_SWGC(ORD)                                                                                                              \
-  if (a.exact_sum) hipLaunchKernelGGL((spline_wg_color_kernel<KIND, ORD, NF, true, NC>), grid, dim3(256), 0, stream, a, map, dst);    \
-  else hipLaunchKernelGGL((spline_wg_color_kernel<KIND, ORD, NF, false, NC>), grid, dim3(256), 0, stream, a, map, dst)
-  switch (a.order) {
-    case 2: DCP_SWGC(2); break;
-    case 3: DCP_SWGC(3); break;
-    case 4: DCP_SWGC(4); break;
-    default: DCP_SWGC(5); break;
-  }
-#undef DCP_SWGC
-  return hipGetLastError();
-}
-
-template <int KIND, int NF>
-static hipError_t launch_wg_color_nf(const SplineArgs& a, const MapArgs& map, int channels, void* dst, hipStream_t stream) {
-  switch (channels) {
-    case 1: return launch_wg_color_nc<KIND, NF, 1>(a, map, dst, stream);
-    case 2: return launch_wg_color_nc<KIND, NF, 2>(a, map, dst, stream);
-    case 3: return launch_wg_color_nc<KIND, NF, 3>(a, map, dst, stream);
-    default: return launch_wg_color_nc<KIND, NF, 4>(a, map, dst, stream);
-  }
-}
-
-// (the polynomial's instantiations as launch_spline_wg: up to five coefficients zero-padded to NF = 5, longer vectors staged in LDS)
 template <int KIND>
 static hipError_t launch_wg_color(const SplineArgs& a_in, const MapArgs& map_in, int channels, void* dst, hipStream_t stream) {
-  SplineArgs a = a_in;
-  a.xcd_remap = get_spline_xcd();
-  if constexpr (KIND == kPersp) {
-    return launch_wg_color_nf<KIND, 0>(a, map_in, channels, dst, stream);
-  } else {
-    if (map_in.nfact > 5) return launch_wg_color_nf<KIND, -1>(a, map_in, channels, dst, stream);
-    MapArgs map = map_in;
-    for (int i = map.nfact < 0 ? 0 : map.nfact; i < 5; ++i) map.fact[i] = 0.0;
-    map.nfact = 5;
-    return launch_wg_color_nf<KIND, 5>(a, map, channels, dst, stream);
-  }
+  return spline_wg_with_nf<KIND>(a_in, map_in, [&](auto nf, const SplineArgs& a, const MapArgs& map) {
+    auto launch = [&](auto nc) {
+      spline_for_order_exact(a, [&](auto ord, auto exact) {
+        hipLaunchKernelGGL((spline_wg_color_kernel<KIND, decltype(ord)::value, decltype(nf)::value, decltype(exact)::value, decltype(nc)::value>), spline_wg_grid(a),
+                           dim3(256), 0, stream, a, map, dst);
+      });
+    };
+    switch (channels) {
+      case 1: launch(std::integral_constant<int, 1>{}); break;
+      case 2: launch(std::integral_constant<int, 2>{}); break;
+      case 3: launch(std::integral_constant<int, 3>{}); break;
+      default: launch(std::integral_constant<int, 4>{}); break;
+    }
+    return hipGetLastError();
+  });
 }
 
 template <int MAPKIND>
 static hipError_t launch_remap_color_order(const SplineArgs& a, const MapArgs& map, int channels, void* dst, hipStream_t stream) {
-  const dim3 grid((unsigned)((a.W + kSplBlock - 1) / kSplBlock), (unsigned)(a.H < 65535 ? a.H : 65535), (unsigned)((a.H + 65534) / 65535));
-  switch (a.order) {
-    case 2: hipLaunchKernelGGL((spline_remap_color_kernel<MAPKIND, 2>), grid, dim3(kSplBlock), 0, stream, a, map, channels, dst); break;
-    case 3: hipLaunchKernelGGL((spline_remap_color_kernel<MAPKIND, 3>), grid, dim3(kSplBlock), 0, stream, a, map, channels, dst); break;
-    case 4: hipLaunchKernelGGL((spline_remap_color_kernel<MAPKIND, 4>), grid, dim3(kSplBlock), 0, stream, a, map, channels, dst); break;
-    default: hipLaunchKernelGGL((spline_remap_color_kernel<MAPKIND, 5>), grid, dim3(kSplBlock), 0, stream, a, map, channels, dst); break;
-  }
+  spline_for_order(a, [&](auto ord) {
+    hipLaunchKernelGGL((spline_remap_color_kernel<MAPKIND, decltype(ord)::value>), spline_remap_grid(a), dim3(kSplBlock), 0, stream, a, map, channels, dst);
+  });
   return hipGetLastError();
 }
 
@@ -422,10 +363,7 @@ hipError_t launch_spline_color(const SplineArgs& a_in, MapKind kind, const MapAr
     if (e != hipSuccess) return e;
   }
   if ((int64_t)a_in.H * a_in.W == 0) return hipSuccess;
-  const bool wg = spline_wg_takes(a_in, kind, map);
-  char name[200];
-  snprintf(name, sizeof(name), "%s + %s<order=%d, channels=%d>", desc, wg ? "spline_wg_color_kernel" : "spline_remap_color_kernel", a_in.order, channels);
-  set_last_kernel_name(name);
+  const bool wg = spline_pick_gather(a_in, kind, map, desc, "_color", "channels", channels);
   if (wg) {
     if (kind == kRadial) return launch_wg_color<kRadial>(a_in, map, channels, dst, stream);
     return launch_wg_color<kPersp>(a_in, map, channels, dst, stream);

@@ -1,5 +1,7 @@
-// spline_device.h -- what the gather kernels of the spline orders share (spline_kernels.hip, spline_color_kernels.hip): the B-spline
-// weights, the folding of a tap index under a boundary mode, and the geometry of the LDS-staged gather.
+// spline_device.h -- the arithmetic every user of the spline orders shares (spline_kernels.hip, spline_color_kernels.hip,
+// spline_frames_kernels.hip, profile_kernels.hip): the B-spline weights, the folding of a tap index under a boundary mode, the
+// LDS-only barrier, and the geometry of the LDS-staged gather.  What only the three gather files share -- box, fill, row table,
+// launchers -- is in spline_gather.h, which needs dcp_device.h.
 #pragma once
 #include "dcp_internal.h"
 
@@ -114,6 +116,11 @@ __device__ __forceinline__ int spline_fold(int i, int n, int mode) {
   if (i < 0) i += s2;
   return i < n ? i : s2 - i;
 }
+
+// Workgroup barrier that orders LDS traffic only: the wave's LDS reads and writes are retired, then the workgroup meets -- what was
+// written may be read, what was read may be overwritten.  (__syncthreads() also drains the wave's global memory operations; a fill of
+// LDS by LDS-DMA is such an operation and needs its own vmcnt wait.)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kSwTW = 128, kSwTH = 32;             // workgroup tile
 constexpr int kSwBoxW = 144, kSwBoxH = 45;         // slab: 144 x 45 float64 = 51 840 B; with the row tables three workgroups per CU

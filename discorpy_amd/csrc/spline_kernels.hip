@@ -15,16 +15,8 @@
 // Lines longer than 256 samples are filtered in overlapping chunks: there GPU and oracle agree to
 // ~1e-24 relative in the coefficients rather than bit for bit.  The gather reads its taps
 // straight from global memory.
-#include "dcp_internal.h"
-#include "dcp_device.h"
+#include "spline_gather.h"
 #include "dcp_lab.h"
-#include "spline_device.h"
-#include <cstdio>
-#include <type_traits>
-
-#ifndef DCP_SPLINE_OUT_AUX
-#define DCP_SPLINE_OUT_AUX 2   // cache-policy bits of spline_wg_kernel's result store: 2 = nt (0: plain, A/B)
-#endif
 
 namespace dcp {
 
@@ -267,10 +259,8 @@ constexpr int kTfWaves = kTfBlock / 64;
 
 DCP_LAB_DEFINITIONS_SPLINE
 
-// Workgroup barrier that orders LDS traffic only (__syncthreads() also drains the wave's global memory operations; the tile
-// lives in LDS and the prefetched values in registers the compiler tracks itself, so the barriers here need lgkmcnt only and
-// the stores of one tile / the loads of the next stay in flight across them).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (The barriers of the prefilter kernels are lds_barrier, spline_device.h: the tile lives in LDS and the prefetched values in registers
+// the compiler tracks itself, so they need lgkmcnt only and the stores of one tile / the loads of the next stay in flight across them.)
 
 template <int AXIS, bool IN_F32, int SAMPLES>
 __global__ void __launch_bounds__(kTfBlock) spline_tile_filter_kernel(const TileFilter f) {
@@ -1387,11 +1377,10 @@ __global__ void __launch_bounds__(kSplBlock) spline_remap_kernel(const SplineArg
 // taps of a pixel are then LDS reads instead of global gathers.  A tile whose box does not fit the slab or reaches
 // over the edge of the coefficient plane (there the taps fold according to the boundary mode) takes the global
 // gather of spline_remap_kernel for all its pixels.  Radial and perspective maps.
-
-// NF: length of the radial polynomial (5: coefficients from the kernel arguments, shorter vectors padded with zeros by the
-// launcher -- fma(r2, 0, a) = a exactly; -1: any length, coefficients staged in LDS).  Phase 1 is remap_wg_kernel's: a row table
-// per wave and the hoisted evaluation map_coord (dcp_device.h) -- round 2 walked the coefficient vector with one scalar load and
-// one wait per coefficient and pixel row.
+// spline_wg_color_kernel and spline_wg_frames_kernel are this kernel with a loop over planes.  spline_gather.h holds what the three
+// share as functions (hull, box rule and `staged`; the fill's extent and first chunk; the row table and NF).  The tile order,
+// issue_fill, the tap sum `value` and the folding gather are written out in each of them, because as functions they change the
+// kernels' code (spline_gather.h); this file holds their commented copy, and a fix to one of them goes to all three.
 template <int KIND, int ORDER, int NF, bool EXACT>
 __global__ void __launch_bounds__(256, ORDER >= 5 ? 2 : 3) spline_wg_kernel(const SplineArgs a, const MapArgs map, void* dst) {
   constexpr int RW = KIND == kRadial ? 2 : 4;
@@ -1419,41 +1408,15 @@ __global__ void __launch_bounds__(256, ORDER >= 5 ? 2 : 3) spline_wg_kernel(cons
   const int y0 = __builtin_amdgcn_readfirstlane(ty * kSwTH + wy * 16);
   const int x = tx * kSwTW + wx * 64 + lane;
   const float wmaxf = (float)(a.W - 1), hmaxf = (float)(a.H - 1);
-  // ---- corner pixels (lanes 0..3) -> hull of their taps' base positions in the padded plane
-  int cx0, cx1, cy0, cy1;
-  {
-    const double X = (double)min(tx * kSwTW + (lane & 1) * (kSwTW - 1), a.W - 1);
-    const double Y = (double)min(ty * kSwTH + ((lane >> 1) & 1) * (kSwTH - 1), a.H - 1);
-    double xd, yd;
-    corner_coord<KIND, NF>(map, X, Y, &xd, &yd);
-    const int cxi = (int)round_clip_f32(xd, wmaxf) + a.pad, cyi = (int)round_clip_f32(yd, hmaxf) + a.pad;
-    const int xa = __builtin_amdgcn_readlane(cxi, 0), xb = __builtin_amdgcn_readlane(cxi, 1);
-    const int xc_ = __builtin_amdgcn_readlane(cxi, 2), xd_ = __builtin_amdgcn_readlane(cxi, 3);
-    const int ya = __builtin_amdgcn_readlane(cyi, 0), yb = __builtin_amdgcn_readlane(cyi, 1);
-    const int yc_ = __builtin_amdgcn_readlane(cyi, 2), yd_ = __builtin_amdgcn_readlane(cyi, 3);
-    cx0 = min(min(xa, xb), min(xc_, xd_));
-    cx1 = max(max(xa, xb), max(xc_, xd_));
-    cy0 = min(min(ya, yb), min(yc_, yd_));
-    cy1 = max(max(ya, yb), max(yc_, yd_));
-  }
-  // floor(coordinate) lies in [c0 - 1, c1 + 1]; odd orders tap floor - ORDER/2 .. + ORDER, even orders
-  // floor(coordinate + 0.5) - ORDER/2 .. + ORDER: all inside [c0 - 1 - ORDER/2, c1 + 2 + (ORDER + 1)/2]
-  const int bx0 = cx0 - 1 - ORDER / 2, bx1 = cx1 + 2 + (ORDER + 1) / 2;
-  const int by0 = cy0 - 1 - ORDER / 2, by1 = cy1 + 2 + (ORDER + 1) / 2;
-  const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-  // staged: the box fits the slab and lies inside the plane (no tap folds); workgroup-uniform
-  const bool staged = bw <= kSwBoxW && bh <= kSwBoxH && bx0 >= 0 && by0 >= 0 && bx1 <= a.Wp - 1 && by1 <= a.Hp - 1;
-  // the fill's descriptor ends with the box's last row: a chunk of a later row is out of range (zeros, no memory access), which
-  // replaces a per-lane row test in every load (remap_wg_kernel)
-  const uint32_t rstep = (uint32_t)a.Wp * 8u;
-  const unsigned long long plane_bytes = (unsigned long long)a.Hp * rstep, rows_end = (unsigned long long)(by1 + 1) * rstep;
-  const __amdgpu_buffer_rsrc_t src_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.coef, 0, (int)(uint32_t)(staged && rows_end < plane_bytes ? rows_end : plane_bytes), 0x00020000);
-  const int fc = wave * 64 + lane;
-  const int crow0 = fc / kSwCH;
-  const int c160 = fc - crow0 * kSwCH;
-  const uint32_t off0 = ((uint32_t)by0 * (uint32_t)a.Wp + (uint32_t)bx0) * 8u + (uint32_t)crow0 * rstep + (uint32_t)c160 * 16u;
-  const int nchunk = bh * kSwCH;
+  // ---- corner hull -> box of every tap of the tile -> staged (spline_gather.h)
+  const SwBox box = sw_box<KIND, ORDER, NF>(a, map, tx, ty, lane);
+  const int bx0 = box.bx0, by0 = box.by0;
+  const bool staged = box.staged;
+  // the fill (spline_gather.h): its descriptor ends with the box's last row
+  const __amdgpu_buffer_rsrc_t src_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.coef, 0, (int)sw_fill_extent(a, box), 0x00020000);
+  const SwFill fill = sw_fill(a, box, wave, lane);
+  const uint32_t rstep = fill.rstep, off0 = fill.off0;
+  const int c160 = fill.c160, nchunk = fill.nchunk;
   auto issue_fill = [&](auto jc) {
     constexpr int j = decltype(jc)::value;
     if constexpr (j < kSwNJ) {
@@ -1474,12 +1437,8 @@ __global__ void __launch_bounds__(256, ORDER >= 5 ? 2 : 3) spline_wg_kernel(cons
       }
     }
   };
-  // ---- row table of this wave's 16 rows (lanes 0..15; same-wave LDS traffic is ordered, no barrier)
-  if (lane < 16) fill_row<KIND, RW>(map, s_row[wave], lane, (double)min(y0 + lane, a.H - 1));
-  if constexpr (NF < 0 && KIND != kPersp) {
-    if ((int)threadIdx.x < map.nfact) s_coef[threadIdx.x] = map.fact[threadIdx.x];
-    __syncthreads();
-  }
+  // ---- row table of this wave's 16 rows, a long polynomial into LDS (spline_gather.h)
+  sw_stage_rows<KIND, NF, RW>(a, map, s_row, s_coef, wave, lane, y0);
   // ---- phase 1: the float32 coordinates of this wave's 16 rows, a load going out in front of each of the first 13
   const int rows = __builtin_amdgcn_readfirstlane(max(0, min(16, a.H - y0)));
   const ColCtx col = make_col<KIND, NF>(map, min(x, a.W - 1));
@@ -1585,50 +1544,24 @@ __global__ void __launch_bounds__(256, ORDER >= 5 ? 2 : 3) spline_wg_kernel(cons
   }
 }
 
-template <int KIND, int NF>
-static hipError_t launch_spline_wg_nf(const SplineArgs& a, const MapArgs& map, void* dst, hipStream_t stream) {
-  const unsigned tiles_x = (unsigned)((a.W + kSwTW - 1) / kSwTW);
-  const dim3 grid(a.xcd_remap ? ((tiles_x + 7u) / 8u) * 8u : tiles_x, (unsigned)((a.H + kSwTH - 1) / kSwTH));
-#define DCP_SWG(ORD)                                                                                                        \
-  if (a.exact_sum) hipLaunchKernelGGL((spline_wg_kernel<KIND, ORD, NF, true>), grid, dim3(256), 0, stream, a, map, dst);    \
-  else hipLaunchKernelGGL((spline_wg_kernel<KIND, ORD, NF, false>), grid, dim3(256), 0, stream, a, map, dst)
-  switch (a.order) {
-    case 2: DCP_SWG(2); break;
-    case 3: DCP_SWG(3); break;
-    case 4: DCP_SWG(4); break;
-    default: DCP_SWG(5); break;
-  }
-#undef DCP_SWG
-  return hipGetLastError();
-}
-
 template <int KIND>
 static hipError_t launch_spline_wg(const SplineArgs& a_in, const MapArgs& map_in, void* dst, hipStream_t stream) {
-  SplineArgs a = a_in;
-  a.xcd_remap = g_spline_xcd;
-  if constexpr (KIND == kPersp) {
-    return launch_spline_wg_nf<KIND, 0>(a, map_in, dst, stream);          // (no polynomial)
-  } else {
-    if (map_in.nfact > 5) return launch_spline_wg_nf<KIND, -1>(a, map_in, dst, stream);
-    MapArgs map = map_in;                                                 // <= 5 coefficients: the NF = 5 instantiation, zero-padded
-    for (int i = map.nfact < 0 ? 0 : map.nfact; i < 5; ++i) map.fact[i] = 0.0;
-    map.nfact = 5;
-    return launch_spline_wg_nf<KIND, 5>(a, map, dst, stream);
-  }
+  return spline_wg_with_nf<KIND>(a_in, map_in, [&](auto nf, const SplineArgs& a, const MapArgs& map) {
+    spline_for_order_exact(a, [&](auto ord, auto exact) {
+      hipLaunchKernelGGL((spline_wg_kernel<KIND, decltype(ord)::value, decltype(nf)::value, decltype(exact)::value>), spline_wg_grid(a), dim3(256), 0, stream, a,
+                         map, dst);
+    });
+    return hipGetLastError();
+  });
 }
 
 template <int MAPKIND>
 static hipError_t launch_remap_order(const SplineArgs& a, const MapArgs& map, const CoordArgs& ca, void* dst,
                                      int64_t total, hipStream_t stream) {
-  const dim3 grid = MAPKIND == 2 ? dim3((unsigned)((total + kSplBlock - 1) / kSplBlock))
-                                 : dim3((unsigned)((a.W + kSplBlock - 1) / kSplBlock), (unsigned)(a.H < 65535 ? a.H : 65535),
-                                        (unsigned)((a.H + 65534) / 65535));
-  switch (a.order) {
-    case 2: hipLaunchKernelGGL((spline_remap_kernel<MAPKIND, 2>), grid, dim3(kSplBlock), 0, stream, a, map, ca, dst); break;
-    case 3: hipLaunchKernelGGL((spline_remap_kernel<MAPKIND, 3>), grid, dim3(kSplBlock), 0, stream, a, map, ca, dst); break;
-    case 4: hipLaunchKernelGGL((spline_remap_kernel<MAPKIND, 4>), grid, dim3(kSplBlock), 0, stream, a, map, ca, dst); break;
-    default: hipLaunchKernelGGL((spline_remap_kernel<MAPKIND, 5>), grid, dim3(kSplBlock), 0, stream, a, map, ca, dst); break;
-  }
+  const dim3 grid = MAPKIND == 2 ? dim3((unsigned)((total + kSplBlock - 1) / kSplBlock)) : spline_remap_grid(a);
+  spline_for_order(a, [&](auto ord) {
+    hipLaunchKernelGGL((spline_remap_kernel<MAPKIND, decltype(ord)::value>), grid, dim3(kSplBlock), 0, stream, a, map, ca, dst);
+  });
   return hipGetLastError();
 }
 
@@ -1910,12 +1843,7 @@ hipError_t launch_spline(const SplineArgs& a, MapKind kind, const MapArgs& map, 
   if (e != hipSuccess) return e;
   const int64_t total = kind == kCoords ? ca.npts : (int64_t)a.H * a.W;
   if (total == 0) return hipSuccess;
-  const bool wg = spline_wg_takes(a, kind, map);
-  {
-    char name[160];
-    snprintf(name, sizeof(name), "%s + %s<order=%d>", desc, wg ? "spline_wg_kernel" : "spline_remap_kernel", a.order);
-    set_last_kernel_name(name);
-  }
+  const bool wg = spline_pick_gather(a, kind, map, desc, "", nullptr, 0);
   if (wg) {
     if (kind == kRadial) return launch_spline_wg<kRadial>(a, map, dst, stream);
     return launch_spline_wg<kPersp>(a, map, dst, stream);
