@@ -93,6 +93,10 @@ def slope(**o):
     return F.lib().dcp_window_slope_rows(*a.values())
 
 
+# 65536 rows of one sample and a destination of that shape: a refusal for the number of rows comes behind the overlap check
+MANY = np.zeros((65536, 1), np.float32)
+OUT_MANY = np.full(65536 * 4, SENTINEL, np.uint8)
+
 COORD = np.zeros((2, 40))
 BAND = np.array([0, 1], np.int32), np.array([2, 2], np.int32)
 _i32 = F.C.POINTER(F.C.c_int32)
@@ -126,6 +130,7 @@ REFUSALS = [
     (slope, dict(dtype=U16), UNS, "profiles are float32 or float64"),
     (slope, dict(dst=None), INV, "null src / dst"),
     (slope, dict(length=0), INV, "height and width must be at least 1"),
+    (slope, dict(src=MANY.ctypes.data, dst=OUT_MANY.ctypes.data, nrows=65536, length=1, stride=1), UNS, "more than 65535 rows"),
     (profiles, dict(dtype=U16), UNS, "profiles are float32 or float64"),
     (profiles, dict(dst=None), INV, "null dst / coordinate / band pointer"),
     (profiles, dict(yc=None), INV, "null dst / coordinate / band pointer"),
@@ -146,7 +151,7 @@ def test_entry_points_refuse_before_any_device_work(fn, override, code, fragment
     OUT[:] = SENTINEL
     assert fn(**override) == code
     assert fragment in F.last_error(), F.last_error()
-    assert (OUT == SENTINEL).all()
+    assert (OUT == SENTINEL).all() and (OUT_MANY == SENTINEL).all()
 
 
 def test_wrappers_refuse_before_any_device_work(lp):

@@ -82,8 +82,9 @@ def test_peak_tables_integer_positions(lp):
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_peak_search_of_73_rows(lp, dtype):
-    """73 rows of 513 samples (three steps of the row's workgroup) at radius 11 and at 128: row 0 against the fixture, rows 1, 36 and 72
-    (the same samples rotated) against the restated search."""
+    """73 rows of 513 samples at radius 11 (samples 11 .. 500: two steps of the row's workgroup) and at 128 (samples 128 .. 383: one
+    step): row 0 against the fixture, rows 1, 36 and 72 (the same samples rotated) against the restated search.  Rows of up to five
+    steps are in tests/test_peak_steps_gpu.py."""
     g = G()
     for k in range(NTABLES):
         row, radius, sens = table(k)
