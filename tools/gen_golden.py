@@ -111,6 +111,283 @@ if "--plane-refusals" in sys.argv[1:]:
     raise SystemExit(0)
 
 
+# ---- G30: discorpy.proc.processing (what discorpy_amd/proc/processing.py restates): what every public function of the reference's
+# module returns on three sets of grouped lines, the float32 tables under them, and the metric matrices of find_cod_fine.
+#   A  the reference's own unit-test grid (tests/test_processing.py): 31 x 31 points at pitch 2, moved along their rays from
+#      (33, 35) by 1 - 2e-3 r; point_dist 2;
+#   B  the lines the reference grouped from G29's image a at roi 0.9 (hor2 / ver2: after the residual filter), point_dist its dist;
+#   C  a 13 x 18 grid at pitch 32 in a 480 x 640 frame, centre (300, 250), factor 1 - 8e-5 r, Gaussian noise of 0.3 px (seed in the
+#      file); P is the same points pushed through a mild homography (G30_HOMOGRAPHY).
+# find_cod_fine depends on where BFGS stops (the metric minimises per line and candidate), so a case is recorded only where the
+# reference's own choice is stable: on both passes, the gap between the smallest and the second-smallest entry of its metric matrix is
+# at least 10 times the largest difference between that matrix and the same matrix with the exact minimiser (the real roots of the
+# cubic derivative).  C's seed is the first from G30_FIRST_SEED on that passes; B is left out of that one function if it does not.
+# Runs alone as   python tools/gen_golden.py --g30   (it needs g29_dot_grid.npz, which a full run writes before it).
+G30_HOMOGRAPHY = [1.0, 0.012, 2.0, -0.009, 1.0, 3.0, 2.0e-5, -3.0e-5]
+G30_FIRST_SEED = 3000
+G30_RATIO = 10.0
+
+
+def g30():
+    import inspect
+    import time
+    import types
+    import warnings
+
+    def split(pts, lens):
+        return np.split(f64(pts), np.cumsum(lens)[:-1])
+
+    def radial_grid(ys, xs, xc, yc, k):
+        y, x = np.meshgrid(f64(ys), f64(xs), indexing="ij")
+        r = np.sqrt((x - xc) ** 2 + (y - yc) ** 2)
+        fact = 1.0 - k * r
+        return np.stack([yc + (y - yc) * fact, xc + (x - xc) * fact], axis=-1)          # (rows, columns, 2) of (y, x)
+
+    def lines_of(grid):
+        return [np.array(row) for row in grid], [np.array(col) for col in grid.transpose(1, 0, 2)]
+
+    def homography(grid, c):
+        y, x = grid[..., 0], grid[..., 1]
+        den = c[6] * x + c[7] * y + 1.0
+        return np.stack([(c[3] * x + c[4] * y + c[5]) / den, (c[0] * x + c[1] * y + c[2]) / den], axis=-1)
+
+    class ExactMinimiser:
+        """Stands in for scipy.optimize inside the reference's _calc_error: the global minimum of t**2 + (a t**2 + b t + c)**2."""
+        @staticmethod
+        def minimize(fun, x0, args=()):
+            a, b, c = (np.float64(v) for v in args)
+            roots = np.roots([2 * a * a, 3 * a * b, b * b + 2 * a * c + 1.0, b * c])
+            real = roots[np.abs(roots.imag) < 1e-9 * (1.0 + np.abs(roots.real))].real
+            return types.SimpleNamespace(x=np.array([real[np.argmin(fun(real, a, b, c))]]))
+
+    def metric_matrix(hor, ver, xc, yc, shifts, exact):
+        """The matrix inside the reference's _calc_metric: its own code runs, _calc_error's return values are collected."""
+        values, inner, solver = [], proc._calc_error, proc.optimize
+
+        def recorder(ch, cv):
+            values.append(inner(ch, cv))
+            return values[-1]
+        proc._calc_error = recorder
+        if exact:
+            proc.optimize = ExactMinimiser
+        try:
+            chosen = proc._calc_metric(hor, ver, xc, yc, shifts, shifts)
+        finally:
+            proc._calc_error, proc.optimize = inner, solver
+        mat = np.asarray(values, dtype=np.float32).reshape(len(shifts), len(shifts)).T          # filled [i, j] with j outermost
+        row, col = np.unravel_index(mat.argmin(), mat.shape)
+        assert (shifts[col], shifts[row]) == chosen
+        return mat, (int(row), int(col))
+
+    def fine_search(hor, ver, xc, yc, point_dist):
+        """(recorded arrays, the two ratios) of find_cod_fine from (xc, yc)."""
+        rec, ratios = {}, []
+        cx, cy = xc, yc
+        for name, shifts in (("pass1", np.arange(-point_dist, point_dist + 2.0, 2.0)), ("pass2", np.arange(-2.0, 2.5, 0.5))):
+            mat, (row, col) = metric_matrix(hor, ver, cx, cy, shifts, False)
+            exact, _ = metric_matrix(hor, ver, cx, cy, shifts, True)
+            two = np.sort(mat.astype(np.float64).ravel())[:2]
+            gap, moved = two[1] - two[0], np.abs(mat.astype(np.float64) - exact.astype(np.float64)).max()
+            ratios.append(gap / moved)
+            rec["metric_" + name], rec["index_" + name], rec["gap_" + name] = mat, np.array([row, col], np.int64), np.float64(gap)
+            cx, cy = cx + shifts[col], cy + shifts[row]
+        t0 = time.perf_counter()
+        got = proc.find_cod_fine(hor, ver, xc, yc, point_dist)
+        rec["seconds"] = np.float64(time.perf_counter() - t0)
+        assert got == (cx, cy)
+        rec["center"], rec["ratios"], rec["start"], rec["point_dist"] = f64(got), f64(ratios), f64([xc, yc]), np.float64(point_dist)
+        return rec, ratios
+
+    def groups_present(hor, ver, xc, yc):
+        ch, cv = proc._para_fit_hor(hor, xc, yc)[0], proc._para_fit_ver(ver, xc, yc)[0]
+        return all(n > 0 for n in ((ch[:, 0] > 0).sum(), (ch[:, 0] < 0).sum(), (cv[:, 0] > 0).sum(), (cv[:, 0] < 0).sum()))
+
+    out = {}
+
+    def lines_out(key, lines):
+        out[key + "_pts"] = f64(np.concatenate(lines))
+        out[key + "_len"] = np.array([len(line) for line in lines], np.int64)
+
+    def tag(v):
+        return v if isinstance(v, str) else "f%g" % v
+
+    # ---- the line sets
+    ticks = np.arange(1, 63, 2.0)
+    hor_a, ver_a = lines_of(radial_grid(ticks, ticks, 33.0, 35.0, 2e-3))
+    g29 = np.load(os.path.join(OUT, "g29_dot_grid.npz"))
+    hor_b, ver_b = split(g29["hor2_a_90_pts"], g29["hor2_a_90_len"]), split(g29["ver2_a_90_pts"], g29["ver2_a_90_len"])
+    clean_c = radial_grid(np.arange(40, 480 - 40 + 1, 32), np.arange(40, 640 - 40 + 1, 32), 300.0, 250.0, 8e-5)
+    assert clean_c.shape == (13, 18, 2)
+    point_dist_c = 6.0
+    for seed in range(G30_FIRST_SEED, G30_FIRST_SEED + 40):
+        noisy = clean_c + np.random.default_rng(seed).normal(0.0, 0.3, clean_c.shape)
+        hor_c, ver_c = lines_of(noisy)
+        xc, yc = (float(v) for v in proc.find_cod_coarse(hor_c, ver_c))
+        fine_c, ratios = fine_search(hor_c, ver_c, xc, yc, point_dist_c)
+        print("g30 C seed %d: ratios %.3g %.3g, %.2f s" % (seed, ratios[0], ratios[1], fine_c["seconds"]))
+        if min(ratios) >= G30_RATIO:
+            break
+    else:
+        raise AssertionError("no seed passes the condition")
+    out["c_seed"], out["homography"] = np.int64(seed), f64(G30_HOMOGRAPHY)
+    hor_p, ver_p = lines_of(homography(noisy, G30_HOMOGRAPHY))
+    sets = {"a": (hor_a, ver_a, 2.0), "b": (hor_b, ver_b, float(g29["dist_a_90"])), "c": (hor_c, ver_c, point_dist_c),
+            "p": (hor_p, ver_p, point_dist_c)}
+    centers = {}
+    for key, (hor, ver, dist) in sets.items():
+        lines_out(key + "_hor", hor)
+        lines_out(key + "_ver", ver)
+        out[key + "_point_dist"] = np.float64(dist)
+        # ---- centres; every later call takes the coarse centre as Python floats
+        coarse = proc.find_cod_coarse(hor, ver)
+        out[key + "_coarse"] = f64(coarse)
+        xc, yc = centers[key] = (float(coarse[0]), float(coarse[1]))
+        for it in (1, 2):
+            out["%s_bailey_it%d" % (key, it)] = f64(proc.find_cod_bailey(hor, ver, iteration=it))
+        # ---- float32 tables
+        out[key + "_para_hor"], shifted = proc._para_fit_hor(hor, xc, yc)
+        out[key + "_para_ver"] = proc._para_fit_ver(ver, xc, yc)[0]
+        assert out[key + "_para_hor"].dtype == np.float32 and shifted[0].dtype == np.float64
+        out[key + "_linear_hor"], out[key + "_linear_ver"] = proc._generate_linear_coef(hor, ver)
+        out[key + "_linear_hor_center"], out[key + "_linear_ver_center"] = proc._generate_linear_coef(hor, ver, xc, yc)
+        # ---- undistorted intercepts and the three radial fits
+        for opt in (False, True):
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                out["%s_uc_hor_opt%d" % (key, opt)], out["%s_uc_ver_opt%d" % (key, opt)] = proc._calc_undistor_intercept(
+                    hor, ver, xc, yc, optimizing=opt)
+                for nf in (3, 5):
+                    name = "%s_nf%d_opt%d" % (key, nf, opt)
+                    out["backward_" + name] = proc.calc_coef_backward(hor, ver, xc, yc, nf, optimizing=opt)
+                    out["forward_" + name] = proc.calc_coef_forward(hor, ver, xc, yc, nf, optimizing=opt)
+                    out["bff_f_" + name], out["bff_b_" + name] = proc.calc_coef_backward_from_forward(hor, ver, xc, yc, nf, optimizing=opt)
+            out["%s_warned_opt%d" % (key, opt)] = np.bool_(any(issubclass(w.category, UserWarning) for w in caught))
+        # ---- the reversed model of the backward fit, on the default grid and on the case's own points
+        own = np.concatenate(shifted + proc._para_fit_ver(ver, xc, yc)[1])
+        for nf in (3, 5):
+            back = out["backward_%s_nf%d_opt0" % (key, nf)]
+            out["transform_%s_nf%d_default_backward" % (key, nf)] = proc.transform_coef_backward_and_forward(back)
+            out["transform_%s_nf%d_default_forward" % (key, nf)] = proc.transform_coef_backward_and_forward(back, mapping="forward")
+            out["transform_%s_nf%d_points_backward" % (key, nf)] = proc.transform_coef_backward_and_forward(back, ref_points=own)
+            out["transform_%s_nf%d_points_forward" % (key, nf)] = proc.transform_coef_backward_and_forward(back, mapping="forward", ref_points=own)
+        # ---- what post makes of the calibration (the reference's own functions), for the image-to-calibration test
+        back3 = out["backward_%s_nf3_opt0" % key]
+        out[key + "_check_hor"] = np.bool_(post.check_distortion(post.calc_residual_hor(post.unwarp_line_backward(hor, xc, yc, back3), xc, yc)))
+        out[key + "_check_ver"] = np.bool_(post.check_distortion(post.calc_residual_ver(post.unwarp_line_backward(ver, xc, yc, back3), xc, yc)))
+        # ---- regenerated grids
+        out[key + "_grid_linear_hor"], out[key + "_grid_linear_ver"] = proc.regenerate_grid_points_linear(hor, ver)
+        gh, gv = proc.regenerate_grid_points_linear(out[key + "_linear_hor"], out[key + "_linear_ver"], is_coef=True)
+        assert np.array_equal(gh, out[key + "_grid_linear_hor"]) and np.array_equal(gv, out[key + "_grid_linear_ver"])
+        for pers, find in ((False, False), (False, True), (True, False)):
+            name = "%s_grid_parabola_p%d_c%d" % (key, pers, find)
+            out[name + "_hor"], out[name + "_ver"] = proc.regenerate_grid_points_parabola(hor, ver, perspective=pers, find_center=find)
+            assert out[name + "_hor"].dtype == np.float32 and out[name + "_hor"].shape == (len(hor), len(ver), 2)
+        moved = proc.update_center(shifted, xc, yc)
+        out[key + "_update_center"] = f64(np.concatenate(moved))
+    # ---- a deleted middle line: the warning about missing lines
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        xc, yc = centers["c"]
+        proc.calc_coef_backward(hor_c[:6] + hor_c[7:], ver_c, xc, yc, 3)
+    out["c_warned_line6_deleted"] = np.bool_(any(issubclass(w.category, UserWarning) for w in caught))
+    assert out["c_warned_line6_deleted"] and not out["c_warned_opt0"] and not out["a_warned_opt0"]
+    # ---- find_cod_fine: A, C (its seed was chosen above), B where the condition holds
+    fine_a, ratios_a = fine_search(hor_a, ver_a, *centers["a"], 2.0)
+    assert min(ratios_a) >= G30_RATIO, ratios_a
+    fine_b, ratios_b = fine_search(hor_b, ver_b, *centers["b"], sets["b"][2])
+    print("g30 fine: A ratios %.3g %.3g (%.2f s); B ratios %.3g %.3g (%.2f s)"
+          % (ratios_a[0], ratios_a[1], fine_a["seconds"], ratios_b[0], ratios_b[1], fine_b["seconds"]))
+    fine_cases = [("a", fine_a), ("c", fine_c)] + ([("b", fine_b)] if min(ratios_b) >= G30_RATIO and fine_b["seconds"] < 5.0 else [])
+    out["fine_cases"] = np.array([k for k, _ in fine_cases])
+    out["fine_b_ratios"], out["fine_b_seconds"] = fine_b["ratios"], fine_b["seconds"]          # recorded whether or not B is a case
+    for key, rec in fine_cases:
+        for name, value in rec.items():
+            out["fine_%s_%s" % (key, name)] = value
+    # ---- vanishing points (barrel distortion: A, C and P), and the iteration with the perspective effect taken out
+    for key in ("a", "c", "p"):
+        hor, ver, _ = sets[key]
+        out[key + "_vanishing"] = f64(proc.find_center_based_vanishing_points(hor, ver))
+        assert groups_present(hor, ver, *centers[key])
+    for key in ("c", "p"):
+        hor, ver, _ = sets[key]
+        for it in (1, 2):
+            for method in ("mean", "median", "min", "max"):
+                out["%s_vanishing_it%d_%s" % (key, it, method)] = f64(proc.find_center_based_vanishing_points_iteration(hor, ver, it, method))
+    # the vanishing-point functions took their own way, not Bailey's
+    saved = proc.find_cod_bailey
+
+    def no_bailey(*args, **kwargs):
+        raise AssertionError("fell back to find_cod_bailey")
+    proc.find_cod_bailey = no_bailey
+    try:
+        for key in ("a", "c", "p"):
+            proc.find_center_based_vanishing_points(sets[key][0], sets[key][1])
+        proc.find_center_based_vanishing_points_iteration(hor_p, ver_p, 2, "mean")
+    finally:
+        proc.find_cod_bailey = saved
+    # ---- the perspective route on P: undistorted lines, point pairs, four points, coefficients, corrected lines
+    scales = ("mean", "median", "min", "max", 0.9)
+    for scale in scales:
+        for opt in (False, True):
+            name = "p_undistorted_%s_opt%d" % (tag(scale), opt)
+            out[name + "_hor"], out[name + "_ver"] = proc.generate_undistorted_perspective_lines(hor_p, ver_p, True, scale, opt)
+            out["p_uintercept_%s_opt%d_hor" % (tag(scale), opt)], out["p_uintercept_%s_opt%d_ver" % (tag(scale), opt)] = \
+                proc._calc_undistor_intercept_perspective(hor_p, ver_p, True, scale, opt)
+        name = "p_undistorted_%s_unequal" % tag(scale)
+        out[name + "_hor"], out[name + "_ver"] = proc.generate_undistorted_perspective_lines(hor_p, ver_p, False, scale, True)
+        src, tgt = proc.generate_source_target_perspective_points(hor_p, ver_p, True, scale, True)
+        out["p_source_%s" % tag(scale)], out["p_target_%s" % tag(scale)] = src, tgt
+        for mapping in ("backward", "forward"):
+            out["p_perspective_coef_%s_%s" % (tag(scale), mapping)] = proc.calc_perspective_coefficients(src, tgt, mapping)
+    grid = out["p_grid_linear_hor"]
+    four = np.array([grid[2, 14], grid[10, 3], grid[2, 3], grid[10, 14]])                  # (y, x), in no particular order
+    out["four_points"] = four
+    for order in ("yx", "xy"):
+        given = four if order == "yx" else np.fliplr(four)
+        for equal in (False, True):
+            for scale in ("mean", "min", "max", 0.9):
+                name = "four_%s_eq%d_%s" % (order, equal, tag(scale))
+                out[name + "_source"], out[name + "_target"] = proc.generate_4_source_target_perspective_points(given, order, equal, scale)
+                if order == "yx":
+                    for mapping in ("backward", "forward"):
+                        out[name + "_coef_" + mapping] = proc.calc_perspective_coefficients(out[name + "_source"], out[name + "_target"], mapping)
+    xc, yc = centers["p"]
+    for method in ("mean", "median", "min", "max"):
+        for scale in ("mean", "max", 0.9):
+            got_hor, got_ver = proc.correct_perspective_effect(hor_p, ver_p, xc, yc, method, scale)
+            assert [len(line) for line in got_hor] == [len(line) for line in hor_p]
+            out["p_effect_%s_%s_hor" % (method, tag(scale))] = f64(np.concatenate(got_hor))
+            out["p_effect_%s_%s_ver" % (method, tag(scale))] = f64(np.concatenate(got_ver))
+    # ---- refusals: the exception and its message
+    refused = []
+    for name, call in (("four_three_points", lambda: proc.generate_4_source_target_perspective_points(four[:3])),
+                       ("four_five_points", lambda: proc.generate_4_source_target_perspective_points(np.concatenate([four, four[:1]]))),
+                       ("four_flat_xy", lambda: proc.generate_4_source_target_perspective_points(four.ravel(), "xy")),
+                       ("coef_flat_points", lambda: proc.calc_perspective_coefficients(four.ravel(), four.ravel())),
+                       ("coef_no_points", lambda: proc.calc_perspective_coefficients(np.zeros((0, 2)), np.zeros((0, 2)))),
+                       ("coef_unequal_counts", lambda: proc.calc_perspective_coefficients(four, four[:3]))):
+        try:
+            call()
+        except Exception as err:
+            refused.append((name, type(err).__name__, str(err)))
+        else:
+            raise AssertionError(name + ": the reference accepts it")
+    out["refusal_names"], out["refusal_types"], out["refusal_messages"] = (np.array(col) for col in zip(*refused))
+    # ---- names and signatures
+    names = sorted(n for n, f in inspect.getmembers(proc, inspect.isfunction) if f.__module__ == proc.__name__ and not n.startswith("_"))
+    out["public_names"] = np.array(names)
+    out["signatures"] = np.array([str(inspect.signature(getattr(proc, n))) for n in names])
+    assert "find_cod_fine" in names and "update_center" in names
+    save("g30_proc", **out)
+    size = os.path.getsize(os.path.join(OUT, "g30_proc.npz"))
+    assert size <= 400 << 10, size
+
+
+if "--g30" in sys.argv[1:]:
+    g30()
+    raise SystemExit(0)
+
+
 # ---- G1: the reference's own unwarp_image_backward test input (tests/test_postprocessing.py:77-85)
 hei = wid = 64
 mat = np.zeros((hei, wid), dtype=np.float32)
@@ -1290,4 +1567,5 @@ def g29():
 g27()
 g28()
 g29()
+g30()
 print("done")
