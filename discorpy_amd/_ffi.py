@@ -133,6 +133,8 @@ SIGNATURES = {
     "dcp_threshold_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _dbl, _vp, _int, _int, _vp]),
     "dcp_clear_border_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _int, _vp]),
     "dcp_morph_cross_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
+    "dcp_sort_plane_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _vp]),
+    "dcp_zoom_cubic_nearest_1d": (_int, [_vp, _i64, _vp, _i64, _int, _int, _int, _vp]),
     "dcp_debug_counters": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_bounds": (_int, [C.POINTER(C.c_uint64), _int, _int]),
     "dcp_debug_last_kernel": (C.c_char_p, []),

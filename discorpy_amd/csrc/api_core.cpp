@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) {
 
 const char* last_error() { return g_err; }
 
-std::atomic<int> g_tile_rows{16}, g_xcd_remap{2}, g_coef_lds{0}, g_d_chunk{16}, g_pipe_depth{2}, g_lds_gather{1}, g_stack_chunk_kb{24576}, g_stack_lds{1}, g_host_duplex{1}, g_host_bands{6}, g_tile_cert{1}, g_wg_box{1}, g_wg_per_cu{0}, g_stack_wg{1}, g_int_exact{1}, g_host_direct{1}, g_tall_tiles{0}, g_store_wait{1}, g_fused_wg{1}, g_any_order{0}, g_host_band_sync{0}, g_spline_frames{8}, g_median_lds{1}, g_gauss_lds{1}, g_label_lds{1}, g_hist_lds{1}, g_morph_fused{1};
+std::atomic<int> g_tile_rows{16}, g_xcd_remap{2}, g_coef_lds{0}, g_d_chunk{16}, g_pipe_depth{2}, g_lds_gather{1}, g_stack_chunk_kb{24576}, g_stack_lds{1}, g_host_duplex{1}, g_host_bands{6}, g_tile_cert{1}, g_wg_box{1}, g_wg_per_cu{0}, g_stack_wg{1}, g_int_exact{1}, g_host_direct{1}, g_tall_tiles{0}, g_store_wait{1}, g_fused_wg{1}, g_any_order{0}, g_host_band_sync{0}, g_spline_frames{8}, g_median_lds{1}, g_gauss_lds{1}, g_label_lds{1}, g_hist_lds{1}, g_morph_fused{1}, g_sort_skip{1};
 
 dcp::LaunchOpts current_opts() {
   dcp::LaunchOpts o;
@@ -656,6 +656,8 @@ int dcp_set_option(const char* key_in, int value) {
     g_hist_lds = value ? 1 : 0;       // 0: dcp_histogram_2d adds every run of equal bins to the int64 counts in global memory, at any bin count
   } else if (!strcmp(key, "morph_fused")) {
     g_morph_fused = value ? 1 : 0;    // 0: dcp_morph_cross_2d's opening as two launches (erosion into scratch, then dilation) instead of one
+  } else if (!strcmp(key, "sort_skip")) {
+    g_sort_skip = value ? 1 : 0;      // 0: dcp_sort_plane_2d runs every digit's pass, also those whose digit is the same in every key
   } else if (!strcmp(key, "tile_cert")) {
     g_tile_cert = value ? 1 : 0;      // 0: never use the host's tile-deviation certificate (remap_lds_kernel then votes)
   } else if (!strcmp(key, "stack_chunk_kb")) {
@@ -697,6 +699,7 @@ int dcp_get_option(const char* key_in, int* value) {
   else if (!strcmp(key, "label_lds")) *value = g_label_lds;
   else if (!strcmp(key, "hist_lds")) *value = g_hist_lds;
   else if (!strcmp(key, "morph_fused")) *value = g_morph_fused;
+  else if (!strcmp(key, "sort_skip")) *value = g_sort_skip;
   else if (!strcmp(key, "box_table")) *value = dcp::get_box_table();
   else if (!strcmp(key, "frame_plan")) *value = dcp::get_frame_plan();
   else if (!strcmp(key, "frame_plan_tiles") || !strcmp(key, "frame_plan_exact_tiles")) {

@@ -34,6 +34,7 @@ int make_plane_call(PlaneCall* c, const void* src, void* dst, int height, int wi
   c->dtype = dtype;
   c->esz = (size_t)dcp::elem_size(dtype);
   c->dst_elem = dst_elem;
+  c->dst_n = (int64_t)height * (int64_t)width;
   c->device = device;
   c->stream = (hipStream_t)stream;
   if (!dst_elem) return DCP_OK;
@@ -50,7 +51,7 @@ HostTrip packed_rows(const PlaneCall& c) {
   t.rows = (size_t)c.H;
   t.pitch = (size_t)c.rs * c.esz;
   t.dst = c.dst;
-  t.out_bytes = (size_t)c.H * (size_t)c.W * c.dst_elem;
+  t.out_bytes = (size_t)c.dst_n * c.dst_elem;
   return t;
 }
 

@@ -15,6 +15,7 @@ struct PlaneCall {
   int64_t rs;                // the source's row stride in elements
   int dtype;
   size_t esz, dst_elem;      // element sizes in bytes; dst_elem = 0: no destination
+  int64_t dst_n;             // elements of the destination: H * W unless the entry point says otherwise (dcp_zoom_cubic_nearest_1d)
   bool host;                 // DCP_MEM_HOST
   int device;
   hipStream_t stream;
@@ -49,7 +50,7 @@ struct PlaneDevice {
 // Executes a plane call: selects the device, leases `work_bytes` of the spline workspace (none for 0: work = null) and enqueues
 // launch(src, dst, row_stride, work) -- on the caller's planes for device memory, after which the stream is synchronised iff the entry
 // point returns host scalars (launch enqueues their read-back); on the packed staging planes (row_stride = W) inside the round trip of
-// host memory, which always ends synchronised.  The lease ends before the previous device is selected again.
+// host memory (c.dst_n elements come back), which always ends synchronised.  The lease ends before the previous device is selected again.
 template <typename Launch>
 int run_plane(const PlaneCall& c, bool returns_host_scalars, size_t work_bytes, Launch&& launch) {
   PlaneDevice on(c.device);

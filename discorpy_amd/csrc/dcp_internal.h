@@ -396,6 +396,16 @@ hipError_t launch_morph_cross(const uint8_t* src, uint8_t* dst, uint8_t* tmp, in
 // or kI16; rows w_stride apart) or 1 everywhere where weights is null
 hipError_t launch_label_measures(const void* weights, const int32_t* labels, int H, int W, int64_t w_stride, int64_t l_stride, int dtype, int num,
                                  long long* sums, int32_t* boxes, hipStream_t stream);
+// sort_kernels.hip: dst (dense, H W elements of the type) = the plane's elements in ascending order -- an 8-bit-digit radix sort of
+// order-preserving keys; floats as np.sort orders them (NaNs of either sign last, a negative NaN comes out positive; -0.0 before +0.0).
+// Any ElemType but kBool.  `work`: sort_work_bytes() of device memory (two key buffers, the bins, the plan, the (digit, workgroup)
+// table).  skip = false: the passes whose digit is the same in every key run too (option "x_sort_skip" = 0).  H W < 2^31.
+constexpr int kSortMaxBlocks = 2048;           // workgroups of a pass: the columns of the (digit, workgroup) table
+size_t sort_work_bytes(int64_t n, int dtype);
+hipError_t launch_sort(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, void* work, bool skip, hipStream_t stream);
+// dst[0 .. out_n) = scipy.ndimage.zoom(src, out_n / n, order=3, mode="nearest") of the n elements at src, both of `dtype` (any ElemType
+// but kBool); z_n = pow(sqrt(3) - 2, n + 24) from the host's C library, as scipy computes it.  One launch, no scratch.
+hipError_t launch_zoom_cubic_nearest(const void* src, int64_t n, void* dst, int64_t out_n, int dtype, double z_n, hipStream_t stream);
 // interleaved (H, W, C) image, radial / perspective / fused map, orders 0 / 1; src_cstride = elements between pixels
 hipError_t launch_typed_channels(MapKind kind, const TypedImageArgs& img, const MapArgs& map, int channels, hipStream_t stream);
 // color_kernels.hip: the same on remap_wg_kernel's data path (3 / 4 dense channels of float32 / uint8 / uint16, level-2 certificate of

@@ -20,6 +20,7 @@
 //   median_global_kernel<U, KIND>      the same selection with every tap read from global memory (the reflected index is walked, not
 //                                      divided for): windows whose box fits no tile, and the lab option "x_median_lds" = 0.
 #include "dcp_internal.h"
+#include "order_keys.h"
 
 #include <cstdio>
 
@@ -29,38 +30,6 @@ constexpr int kMedianTW = 64;           // tile width: one wave per tile row
 constexpr int kMedianBlock = 256;       // four waves: four tile rows per pass
 constexpr int kMedianRowsPerPass = kMedianBlock / kMedianTW;
 constexpr size_t kMedianLdsPlain = 64u << 10, kMedianLdsMax = 160u << 10;      // dynamic LDS without / with the function attribute
-
-enum MedianKind : int { kKeyUnsigned = 0, kKeySigned = 1, kKeyFloat = 2 };
-
-template <typename U>
-struct MedianKey {
-  typedef uint32_t type;
-};
-template <>
-struct MedianKey<uint64_t> {
-  typedef uint64_t type;
-};
-
-template <typename U, int KIND>
-__device__ __forceinline__ typename MedianKey<U>::type median_key(U u) {
-  typedef typename MedianKey<U>::type K;
-  constexpr int kBits = (int)sizeof(U) * 8;
-  constexpr K kSign = (K)1 << (kBits - 1), kAll = (K)(~(K)0) >> (sizeof(K) * 8 - kBits);
-  const K k = (K)u;
-  if constexpr (KIND == kKeySigned) return k ^ kSign;
-  if constexpr (KIND == kKeyFloat) return k ^ ((k & kSign) ? kAll : kSign);
-  return k;
-}
-
-template <typename U, int KIND>
-__device__ __forceinline__ U median_elem(typename MedianKey<U>::type k) {
-  typedef typename MedianKey<U>::type K;
-  constexpr int kBits = (int)sizeof(U) * 8;
-  constexpr K kSign = (K)1 << (kBits - 1), kAll = (K)(~(K)0) >> (sizeof(K) * 8 - kBits);
-  if constexpr (KIND == kKeySigned) return (U)(k ^ kSign);
-  if constexpr (KIND == kKeyFloat) return (U)(k ^ ((k & kSign) ? kSign : kAll));
-  return (U)k;
-}
 
 // scipy's "reflect" (d c b a | a b c d | d c b a) for any i: position in the period of 2 n, folded
 __device__ __forceinline__ int median_reflect(int64_t i, int n) {

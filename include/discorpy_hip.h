@@ -617,6 +617,32 @@ int dcp_clear_border_2d(const void* src, uint8_t* dst, int height, int width, lo
 int dcp_morph_cross_2d(const uint8_t* src, uint8_t* dst, int height, int width, long src_row_stride, int op, int mem_kind, int device,
                        void* stream);
 
+/* ---- the image-sized steps of calculate_threshold: the sort of every pixel and the cubic zoom of the sorted list ----
+ * discorpy/prep/preprocessing.py:816-853: np.sort(mat.flatten()), scipy.ndimage.zoom(sorted, size / len, mode="nearest").  Both take
+ * the mem_kind / device / stream triple of dcp_label_2d, DCP_DTYPE_FLOAT32 / FLOAT64 and the 8- to 64-bit integers, and a dst that does
+ * not overlap src; neither synchronises a device call.
+ *
+ * dcp_sort_plane_2d: dst (dense, height * width elements of the source's type, living where the plane lives) = the plane's elements
+ * (rows `src_row_stride` elements apart) in ascending order: np.sort(a, axis=None).  Floats order by value with NaNs of either sign
+ * last.  What NumPy leaves open is fixed here: -0.0 comes before +0.0, NaNs come in the order of their payloads, and a negative NaN comes
+ * out as the positive NaN of the same payload (it loses its sign bit on the way in).  A least-significant-digit radix sort on the eight
+ * bits of a digit over order-preserving integer keys; a pass whose digit is the same in every element is skipped (lab option
+ * "x_sort_skip" = 0: never), so uint8 values stored as float32 cost what their entropy costs.  Work memory: two key buffers (4 bytes per
+ * element up to 32 bits, else 8) and about 2 MiB of tables, leased from the spline workspace; more than its 2 GiB is DCP_ERR_UNSUPPORTED.
+ *
+ * dcp_zoom_cubic_nearest_1d: dst[0 .. out_n) = scipy.ndimage.zoom(src, out_n / n, order=3, mode="nearest") of the 1-D array of n
+ * elements at src; the caller gives the output length scipy would compute (round(n * zoom)).  scipy 1.15's definition: the line
+ * extended by 12 edge samples per side, times the gain, the causal and anticausal recursions of the pole sqrt(3) - 2 with the reflect
+ * boundary's initial values, sampled at j (n - 1) / (out_n - 1) + 12 with scipy's weights in scipy's order, stored as scipy stores a
+ * double into the element type.  Every output point filters a window of 64 samples on either side of its four taps instead of the line:
+ * the start-up error is below 2^-121 of the window's largest magnitude.
+ *
+ * Both: a null pointer, a height, width, n or out_n below 1, a stride below the width, an unknown dtype or mem_kind and src overlapping
+ * dst are DCP_ERR_INVALID_ARG; more than 2^31 - 1 elements, DCP_DTYPE_BOOL and a sort beyond the workspace are DCP_ERR_UNSUPPORTED; all
+ * before any device call. */
+int dcp_sort_plane_2d(const void* src, void* dst, int height, int width, long src_row_stride, int dtype, int mem_kind, int device, void* stream);
+int dcp_zoom_cubic_nearest_1d(const void* src, int64_t n, void* dst, int64_t out_n, int dtype, int mem_kind, int device, void* stream);
+
 /* ---- the per-profile steps of the line-pattern route on batches of profiles (discorpy/prep/linepattern.py:46-274, 512-567) ----
  * The first two take `nrows` profiles of `length` samples as the rows of a DCP_DTYPE_FLOAT32 / FLOAT64 plane (rows `src_row_stride`
  * elements apart) and the mem_kind / device / stream triple of dcp_label_2d.

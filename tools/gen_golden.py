@@ -388,6 +388,121 @@ if "--g30" in sys.argv[1:]:
     raise SystemExit(0)
 
 
+# ---- G31: the rest of discorpy.prep.preprocessing (what discorpy_amd/prep/threshold.py, pointgrid.py and complete.py restate), skimage
+# stubbed as for G26-G30: calculate_threshold on small images of five element types, parabola masks (np.packbits), the point-list
+# functions on recorded points, both polyfit groupings on a barrel-distorted grid, and the module's public names with their signatures.
+# The grid: 15 x 17 points at pitch 40 about (400, 450), pulled towards the centre by 1 / (1 + G31_BARREL r^2) and turned by the slope
+# 0.02 -- strong enough that group_dots_hor_lines / group_dots_ver_lines alone lose outer points (asserted here), weak enough that the
+# polyfit groupings with G31_GROUP return every row and column.  Runs alone as   python tools/gen_golden.py --g31
+G31_BARREL = 3.5e-6
+G31_SLOPE = 0.02
+G31_PITCH = 40.0
+G31_GROUP = dict(ratio=0.15, num_dot_miss=2)
+G31_THRESHOLDS = [("float32", (48, 64), "bright", 2.0), ("float32", (40, 30), "dark", 1.5), ("float64", (40, 56), "bright", 3.0),
+                  ("float64", (33, 47), "dark", 2.0), ("uint8", (96, 128), "bright", 2.0), ("uint8", (50, 70), "dark", 3.0),
+                  ("uint16", (64, 48), "bright", 1.5), ("uint16", (31, 77), "dark", 2.0), ("int16", (48, 64), "bright", 2.0),
+                  ("int16", (45, 45), "dark", 1.5), ("float32", (32, 64), "bright", 2.0)]          # (the last one: a constant middle half)
+G31_MASKS = [dict(height=60, width=80, hor_curviness=0.3, ver_curviness=0.2, hor_margin=(10, 14), ver_margin=(6, 9), rotate=0.0),
+             dict(height=64, width=64, hor_curviness=0.4, ver_curviness=0.4, hor_margin=8, ver_margin=8, rotate=7.5),
+             dict(height=50, width=70, hor_curviness=0.1, ver_curviness=0.1, hor_margin=35, ver_margin=(20, 30), rotate=0.0)]
+
+
+def g31_grid():
+    rows, cols = 15, 17
+    yy, xx = np.meshgrid((np.arange(rows) - rows // 2) * G31_PITCH, (np.arange(cols) - cols // 2) * G31_PITCH, indexing="ij")
+    pull = 1.0 / (1.0 + G31_BARREL * (yy ** 2 + xx ** 2))
+    y, x = yy * pull, xx * pull
+    a = np.arctan(G31_SLOPE)
+    pts = np.column_stack(((y * np.cos(a) + x * np.sin(a) + 400.0).ravel(), (-y * np.sin(a) + x * np.cos(a) + 450.0).ravel()))
+    return pts[np.random.default_rng(7).permutation(len(pts))]
+
+
+def g31():
+    import inspect
+    import types
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    for mod, attr in (("skimage.filters", "threshold_otsu"), ("skimage.segmentation", "clear_border"), ("skimage.transform", "radon")):
+        if not hasattr(sys.modules[mod], attr):
+            setattr(sys.modules[mod], attr, None)
+    import discorpy.prep.preprocessing as ref
+    out = {}
+    # ---- thresholds: a bright (dark) background with a gradient and noise, darker (brighter) dots on it
+    rng = np.random.default_rng(3100)
+    out["thres_dtype"] = np.array([c[0] for c in G31_THRESHOLDS])
+    out["thres_bgr"] = np.array([c[2] for c in G31_THRESHOLDS])
+    out["thres_snr"] = f64([c[3] for c in G31_THRESHOLDS])
+    values = []
+    for i, (dt, shape, bgr, snr) in enumerate(G31_THRESHOLDS):
+        yy, xx = np.mgrid[:shape[0], :shape[1]]
+        base = 0.7 + 0.1 * xx / shape[1] + 0.02 * np.round(rng.standard_normal(shape), 2)
+        dots = ((yy % 12 - 6) ** 2 + (xx % 12 - 6) ** 2) < 9
+        img = np.where(dots, 0.2 + 0.02 * np.round(rng.standard_normal(shape), 2), base)
+        if bgr == "dark":
+            img = 1.0 - img
+        if i == len(G31_THRESHOLDS) - 1:
+            flat = np.sort(img.ravel())
+            flat[len(flat) // 4 - 8:3 * len(flat) // 4 + 8] = flat[len(flat) // 4 - 8]          # the middle half of the sorted values is one number
+            img = flat[rng.permutation(len(flat))].reshape(shape)
+        scale = {"float32": 1.0, "float64": 1.0, "uint8": 255.0, "uint16": 60000.0, "int16": 30000.0}[dt]
+        img = (img * scale - (15000.0 if dt == "int16" else 0.0))
+        img = np.round(img).astype(dt) if np.dtype(dt).kind in "iu" else img.astype(dt)
+        out["thres_img%d" % i] = img
+        values.append(ref.calculate_threshold(img, bgr=bgr, snr=snr))
+    out["thres_value"] = f64(values)
+    assert abs(np.polyfit(np.arange(8.0), np.full(8, 0.5), 1)[0]) < 1e-15
+    # ---- parabola masks and the points they keep
+    pts_rng = np.random.default_rng(3101)
+    for i, kw in enumerate(G31_MASKS):
+        mask = ref.make_parabola_mask(**kw)
+        assert mask.dtype == np.float32 and set(np.unique(mask)) <= {0.0, 1.0}
+        out["mask%d_bits" % i] = np.packbits(mask.astype(bool))
+        # (also above and left of the frame: the truncation of -0.5 is 0, inside; further out the frame test discards the point)
+        pts = np.column_stack((pts_rng.uniform(-5.0, kw["height"] - 0.01, 300), pts_rng.uniform(-5.0, kw["width"] - 0.01, 300)))
+        out["mask%d_points" % i] = pts
+        out["mask%d_kept" % i] = ref.remove_points_using_parabola_mask(pts, **kw)
+    out["mask_args"] = np.array([repr(kw) for kw in G31_MASKS])
+    # ---- rotate_points, remove_subset_points
+    pts = pts_rng.uniform(0.0, 500.0, (40, 2))
+    out["rot_points"] = pts
+    out["rot_deg"] = ref.rotate_points(pts, 12.5)
+    out["rot_rad"] = ref.rotate_points(pts, -0.3, degree_unit=False)
+    out["subset_selected"] = pts[[3, 7, 7, 20]]
+    out["subset_left"] = ref.remove_subset_points(pts[[3, 7, 7, 20]], pts)
+    # ---- the polyfit groupings: the whole grid, two points removed, one outlier added
+    grid = g31_grid()
+    plain_h = sum(len(line) for line in ref.group_dots_hor_lines(grid, G31_SLOPE, G31_PITCH))
+    plain_v = sum(len(line) for line in ref.group_dots_ver_lines(grid, G31_SLOPE, G31_PITCH))
+    assert plain_h < len(grid) and plain_v < len(grid), (plain_h, plain_v)
+    out["grid_plain_counts"] = np.array([plain_h, plain_v], np.int64)
+    holes = np.delete(grid, [10, 100], axis=0)
+    outlier = np.vstack([grid, [[409.0, 463.0]]])
+    for name, pts in (("full", grid), ("holes", holes), ("outlier", outlier)):
+        hor = ref.group_dots_hor_lines_based_polyfit(pts, G31_SLOPE, G31_PITCH, **G31_GROUP)
+        ver = ref.group_dots_ver_lines_based_polyfit(pts, G31_SLOPE, G31_PITCH, **G31_GROUP)
+        print("g31 grid %-8s rows %s columns %s" % (name, [len(line) for line in hor], [len(line) for line in ver]))
+        out["grid_%s_points" % name] = pts
+        for tag, lines in (("hor", hor), ("ver", ver)):
+            out["grid_%s_%s_len" % (name, tag)] = np.array([len(line) for line in lines], np.int64)
+            out["grid_%s_%s" % (name, tag)] = np.vstack(lines)
+    assert list(out["grid_full_hor_len"]) == [17] * 15 and list(out["grid_full_ver_len"]) == [15] * 17
+    # ---- names and signatures
+    names = sorted(n for n, f in inspect.getmembers(ref, inspect.isfunction) if f.__module__ == ref.__name__ and not n.startswith("_"))
+    out["public_names"] = np.array(names)
+    out["signatures"] = np.array([str(inspect.signature(getattr(ref, n))) for n in names])
+    private = ["_get_nearby_hor_points", "_get_nearby_hor_points_iter", "_get_nearby_ver_points", "_get_nearby_ver_points_iter"]
+    out["private_names"] = np.array(private)
+    out["private_signatures"] = np.array([str(inspect.signature(getattr(ref, n))) for n in private])
+    save("g31_prep_rest", **out)
+    size = os.path.getsize(os.path.join(OUT, "g31_prep_rest.npz"))
+    assert size <= 400 << 10, size
+
+
+if "--g31" in sys.argv[1:]:
+    g31()
+    raise SystemExit(0)
+
+
 # ---- G1: the reference's own unwarp_image_backward test input (tests/test_postprocessing.py:77-85)
 hei = wid = 64
 mat = np.zeros((hei, wid), dtype=np.float32)
@@ -1568,4 +1683,5 @@ g27()
 g28()
 g29()
 g30()
+g31()
 print("done")

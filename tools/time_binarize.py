@@ -16,6 +16,9 @@ calls that end in a stream synchronise; the median round, and the rounds' minimu
 The last line is the core clock and package power under the 4096^2 threshold call.
 
     python tools/time_binarize.py [--sides 2048,4096] [--rounds 5] [--reps 10] [--no-scipy]
+
+`--threshold` times the other way to a threshold instead, calculate_threshold and the sort under it (its own --help:
+`python tools/time_binarize.py --threshold --help`).
 """
 import argparse
 import os
@@ -41,7 +44,122 @@ def dot_image(side, radius=8, pitch=40, seed=5):
     return img.astype(np.float32)
 
 
+# --------------------------------------------------------------------------- --threshold: calculate_threshold and its sort
+
+THRESHOLD_DOC = """Time calculate_threshold (discorpy_amd.prep.threshold) and the sort under it on 2048^2 and 4096^2 planes of float32, float64, uint16
+and uint8: a bright background with a gradient and noise, darker dots on a pitch of 40.
+
+Two sides alternate round by round (`--rounds`, at least five; a round is `--reps` back-to-back calls that end synchronised, host clock
+around them), in ms per call with the median round, the rounds' minimum and maximum and the spread:
+
+  * calculate_threshold from a device tensor and from a NumPy array, against the same formula through np.sort / scipy.ndimage.zoom /
+    np.polyfit on this machine's host (one call per round: it takes seconds), with whether the two thresholds are equal;
+  * the sort alone (sort_values of the device tensor) against torch.sort of the same tensor flattened, with whether the outputs are equal
+    and the difference of the medians beside torch.sort's own round-to-round spread.
+
+The last line is the core clock and package power under the 4096^2 float32 sort.
+
+    python tools/time_binarize.py --threshold [--sides 2048,4096] [--dtypes float32,float64,uint16,uint8] [--rounds 5] [--reps 5] [--no-host]
+"""
+
+
+def dot_plane(side, dtype, seed=5):
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:side, 0:side]
+    r2 = ((y + 7) % 40 - 20) ** 2 + ((x + 13) % 40 - 20) ** 2
+    img = np.where(r2 <= 64, 0.2, 0.75 + 0.04 * x / side + 0.02 * y / side) + 0.01 * rng.standard_normal((side, side))
+    scale = {"float32": 1.0, "float64": 1.0, "uint16": 60000.0, "uint8": 250.0}[dtype]
+    img = np.clip(img, 0.0, 1.0) * scale
+    return np.round(img).astype(dtype) if np.dtype(dtype).kind == "u" else img.astype(dtype)
+
+
+def threshold_main():
+    ap = argparse.ArgumentParser(description=THRESHOLD_DOC, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--threshold", action="store_true", help="this mode")
+    ap.add_argument("--sides", default="2048,4096")
+    ap.add_argument("--dtypes", default="float32,float64,uint16,uint8")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--no-host", action="store_true", help="leave out the np.sort / ndi.zoom / np.polyfit side")
+    a = ap.parse_args()
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    import scipy.ndimage as ndi
+    import torch
+    import bench
+    from discorpy_amd import _ffi as F
+    from discorpy_amd.prep import threshold as thr
+    F.require_device()
+
+    def sync():
+        torch.cuda.synchronize()
+
+    def timed(fn, reps):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3 / reps, out
+
+    def alternate(sides):
+        """{name: rounds} and {name: last result} of the callables of `sides` = [(name, fn, reps)], taking turns round by round."""
+        got, last = {name: [] for name, _, _ in sides}, {}
+        for name, fn, _ in sides:
+            for _ in range(a.warmup):
+                fn()
+            sync()
+        for _ in range(a.rounds):
+            for name, fn, reps in sides:
+                ms, last[name] = timed(fn, reps)
+                got[name].append(ms)
+        return got, last
+
+    def line(label, r):
+        print("  %-44s %10.4f ms  (rounds %.4f .. %.4f, spread %.4f)" % (label, float(np.median(r)), min(r), max(r), max(r) - min(r)), flush=True)
+        return float(np.median(r))
+
+    def host_formula(img):
+        profile = ndi.zoom(np.sort(img, axis=None), 1.0 * max(img.shape) / img.size, mode="nearest")
+        return thr._threshold_of_profile(profile, "bright", 2.0)
+
+    clock_plane = None
+    for side in [int(s) for s in a.sides.split(",")]:
+        for dtype in a.dtypes.split(","):
+            img = dot_plane(side, dtype)
+            t = torch.from_numpy(img.view(np.int16) if dtype == "uint16" else img).to("cuda:0")          # (torch sorts int16: the same bits, another order)
+            print("---- %d x %d %s" % (side, side, dtype), flush=True)
+            if dtype == "uint16":
+                dev = F.DeviceArray(img.shape, img.dtype).copy_from_host(img)          # a device array of the plane's own type
+                sides = [("calculate_threshold, device array", lambda: thr.calculate_threshold(dev), a.reps)]
+            else:
+                sides = [("calculate_threshold, device tensor", lambda: thr.calculate_threshold(t), a.reps)]
+            sides.append(("calculate_threshold, NumPy array", lambda: thr.calculate_threshold(img), a.reps))
+            if not a.no_host:
+                sides.append(("np.sort / ndi.zoom / np.polyfit on the host", lambda: host_formula(img), 1))
+            got, last = alternate(sides)
+            med = {name: line(name, r) for name, r in got.items()}
+            values = list(last.values())
+            print("  thresholds %s   equal: %s" % (" ".join("%.9g" % v for v in values), all(v == values[0] for v in values)), flush=True)
+            if not a.no_host:
+                host = med["np.sort / ndi.zoom / np.polyfit on the host"]
+                print("  host / device: %.1f from the device, %.1f from NumPy" % (host / med[sides[0][0]], host / med[sides[1][0]]), flush=True)
+            flat = t.reshape(-1)
+            got, last = alternate([("sort_values (radix sort kernels)", lambda: thr.sort_values(t), a.reps),
+                                   ("torch.sort of the same tensor", lambda: torch.sort(flat).values, a.reps)])
+            ours, theirs = line("sort_values (radix sort kernels)", got["sort_values (radix sort kernels)"]), line("torch.sort of the same tensor", got["torch.sort of the same tensor"])
+            spread = max(got["torch.sort of the same tensor"]) - min(got["torch.sort of the same tensor"])
+            print("  sort_values - torch.sort: %+.4f ms (torch.sort's spread %.4f)   outputs equal: %s" % (
+                ours - theirs, spread, bool(torch.equal(last["sort_values (radix sort kernels)"], last["torch.sort of the same tensor"]))), flush=True)
+            if side >= 4096 and dtype == "float32":
+                clock_plane = t
+    if clock_plane is not None:
+        print("clock under the 4096 x 4096 float32 sort: %s" % (bench.clocks_under_load(lambda: thr.sort_values(clock_plane), sync),), flush=True)
+
+
 def main():
+    if "--threshold" in sys.argv[1:]:
+        return threshold_main()
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
     ap.add_argument("--rounds", type=int, default=5)
