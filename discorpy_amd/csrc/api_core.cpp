@@ -139,7 +139,7 @@ int homography_is_tame(const double* c, int64_t H, int64_t W) {
 // rounded) hull +- the deviation; 0.95 px leaves room for the rounding (one float32 ulp of a coordinate < 2^24).
 namespace {
 constexpr double kTileDevLimit = 0.95;
-constexpr double kWgBoxCols = 144.0, kWgBoxRows = 42.0;     // remap_wg_kernel's slab (unwarp_kernels.hip: kWgBoxW, kWgBoxH)
+constexpr double kWgBoxCols = 144.0, kWgBoxRows = 42.0;     // remap_wg_kernel's slab (unwarp_device.h: kWgBoxW, kWgBoxH)
 // (w^2, h^2) / 8 of the two tile shapes: the 64 x 16 wave tile of remap_lds_kernel, the 128 x 32 workgroup tile of remap_wg_kernel
 constexpr double kSpanX2[2] = {63.0 * 63.0 / 8.0, 127.0 * 127.0 / 8.0}, kSpanY2[2] = {15.0 * 15.0 / 8.0, 31.0 * 31.0 / 8.0};
 
@@ -744,11 +744,14 @@ int dcp_release_scratch(void) {
 
 int dcp_debug_counters(uint64_t* out, int n, int reset) {
   if (!out || n < 2) return fail(DCP_ERR_INVALID_ARG, "need room for 2 counters");
-  unsigned long long v[2];
+  out[0] = out[1] = 0;
   DCP_HIP(hipDeviceSynchronize());
-  DCP_HIP(dcp::read_lds_stats(v, reset != 0));
-  out[0] = v[0];
-  out[1] = v[1];
+  for (auto rd : {dcp::read_lds_stats_unwarp, dcp::read_lds_stats_stack}) {     // the frame kernels' pair and the stack kernels'
+    unsigned long long v[2];
+    DCP_HIP(rd(v, reset != 0));
+    out[0] += v[0];
+    out[1] += v[1];
+  }
   return DCP_OK;
 }
 
@@ -761,9 +764,9 @@ int dcp_debug_bounds(uint64_t* out, int n, int reset) {
 #endif
   out[0] = out[1] = out[2] = out[3] = 0;
   DCP_HIP(hipDeviceSynchronize());
-  hipError_t (*readers[9])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_color, dcp::read_bounds_spline, dcp::read_bounds_spline_color,
-                                                          dcp::read_bounds_spline_frames, dcp::read_bounds_gauss, dcp::read_bounds_label, dcp::read_bounds_fourier,
-                                                          dcp::read_bounds_profile};
+  hipError_t (*readers[10])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_stack, dcp::read_bounds_color, dcp::read_bounds_spline,
+                                                           dcp::read_bounds_spline_color, dcp::read_bounds_spline_frames, dcp::read_bounds_gauss, dcp::read_bounds_label,
+                                                           dcp::read_bounds_fourier, dcp::read_bounds_profile};
   for (auto rd : readers) {
     unsigned long long v[4];
     DCP_HIP(rd(v, reset != 0));

@@ -28,6 +28,7 @@
 #include "dcp_internal.h"
 #include "dcp_device.h"
 #include "dcp_pixel_store.h"
+#include "unwarp_launch.h"
 #include <type_traits>
 #include <cstdio>
 
@@ -64,7 +65,7 @@ struct ColorGeom {
   static constexpr int kSlabBytes = NJ * 256 * 16;
 };
 
-// One blend of the four taps of a channel, in the arithmetic of `SAMPLER` (finish() of unwarp_kernels.hip, restated for
+// One blend of the four taps of a channel, in the arithmetic of `SAMPLER` (finish() of unwarp_device.h, restated for
 // any element type; EDGE: the far-edge rule of scipy's zero-weight tap, see there).
 template <int SAMPLER, typename T, bool EDGE>
 __device__ __forceinline__ T blend4(T t00, T t01, T t10, T t11, float fxf, float fyf) {
@@ -361,11 +362,8 @@ template <int KIND, int NF, int SAMPLER, typename T, int NC, int SHAPE = 0>
 static hipError_t launch_color_t(const ImageArgs& img_in, const MapArgs& map, hipStream_t stream) {
   using S = TileShape<SHAPE>;
   ImageArgs img = img_in;
-  img.tiles_x = (img.W + S::TW - 1) / S::TW;
-  img.tiles_y = (img.rows_out + S::TH - 1) / S::TH;
-  // XCD stripes of whole tile columns only when they balance (see launch_wg in unwarp_kernels.hip)
-  if (img.xcd_remap != 2 || 8 * ((img.tiles_x + 7) / 8) * 100 > img.tiles_x * 107) img.xcd_remap = 0;
-  const dim3 grid(img.xcd_remap == 2 ? 8 * ((img.tiles_x + 7) / 8) : img.tiles_x, img.tiles_y);
+  // (img.xcd_remap is 0 or 2 here: launch_color copies the option and turns 1 away)
+  const dim3 grid = wg_tile_grid(&img, S::TW, S::TH);
   char name[96];
   // (the radial map is not named: its kernels keep the names they had before the other maps came; as the single-plane names otherwise)
   snprintf(name, sizeof(name), "remap_wg_color_kernel<%sNF=%d,%s,%s x %d%s>", KIND == kRadial ? "" : KIND == kPersp ? "Persp," : "Fused,", NF,
@@ -377,22 +375,13 @@ static hipError_t launch_color_t(const ImageArgs& img_in, const MapArgs& map, hi
   return hipGetLastError();
 }
 
-// coefficient vectors shorter than the instantiated length are padded with zeros: fma(r2, 0, a) = a exactly, so every
-// intermediate of the even / odd Horner chains, and the result, is unchanged (as launch_wg_batch_t / pad4)
-static MapArgs pad_to(const MapArgs& m, int n) {
-  MapArgs p = m;
-  for (int i = p.nfact < 0 ? 0 : p.nfact; i < n; ++i) p.fact[i] = 0.0;
-  if (p.nfact < n) p.nfact = n;
-  return p;
-}
-
 template <int KIND, int SAMPLER, typename T, int NC, int SHAPE = 0>
 static hipError_t launch_color_n(const ImageArgs& img, const MapArgs& map, hipStream_t stream) {
   if constexpr (KIND == kPersp) {                  // no polynomial: one instantiation
     return launch_color_t<kPersp, 0, SAMPLER, T, NC, SHAPE>(img, map, stream);
   } else {
-    if (map.nfact <= 5) return launch_color_t<KIND, 5, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 5), stream);
-    if (map.nfact <= 10) return launch_color_t<KIND, 10, SAMPLER, T, NC, SHAPE>(img, pad_to(map, 10), stream);
+    if (map.nfact <= 5) return launch_color_t<KIND, 5, SAMPLER, T, NC, SHAPE>(img, pad_to<5>(map), stream);
+    if (map.nfact <= 10) return launch_color_t<KIND, 10, SAMPLER, T, NC, SHAPE>(img, pad_to<10>(map), stream);
     return launch_color_t<KIND, -1, SAMPLER, T, NC, SHAPE>(img, map, stream);
   }
 }

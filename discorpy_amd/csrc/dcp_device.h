@@ -620,7 +620,7 @@ __device__ __forceinline__ T to_elem(double t) {
   }
 }
 
-// ------------------------------------------------------------------ integer element types: the exact lerp (see unwarp_kernels.hip, exact_lerp_pairs)
+// ------------------------------------------------------------------ integer element types: the exact lerp (see unwarp_device.h, exact_lerp_pairs)
 constexpr float kExactLerpMinCoord = 32.0f;
 // The same blend with the four taps read as NARROW elements straight from LDS (ds_read_u16 / _i16 / _u8 / _i8: naturally aligned,
 // no pair extraction): 4 LDS reads instead of 2, and 6 VALU instructions fewer per pixel (no aligned-dword address, shift count,

@@ -1,4 +1,4 @@
-// dcp_internal.h -- shared between the HIP kernels (unwarp_kernels.hip) and the
+// dcp_internal.h -- shared between the HIP kernels (unwarp_kernels.hip, stack_kernels.hip, ...) and the
 // C-ABI layer (api_*.cpp).  Not installed; the public surface is
 // include/discorpy_hip.h.
 #pragma once
@@ -155,7 +155,7 @@ struct LaunchOpts {
                            // while earlier packets of its stream still run (DCP_MEM_DEVICE_UNORDERED; the caller vouches for independence)
 };
 
-// launchers (unwarp_kernels.hip)
+// launchers: frames (unwarp_kernels.hip) and stacks (stack_kernels.hip: launch_stack*, stack_wg_would_take)
 hipError_t launch_image(MapKind kind, const ImageArgs& img, const MapArgs& map, int sampler,
                         bool round_f32, const LaunchOpts& opts, hipStream_t stream);
 // one frame of launch_image_batch (host side): its own source, destination, centre and coefficient vector
@@ -192,9 +192,12 @@ hipError_t launch_stack(const StackArgs& st, const MapArgs& map, int sampler, bo
 hipError_t launch_stack_centres(const StackArgs& st, const MapArgs& map, const double* xcs, const double* ycs, int ncentres, int sampler,
                                 bool round_f32, const LaunchOpts& opts, hipStream_t stream);
 
-hipError_t read_lds_stats(unsigned long long* out, bool reset);
+// tiles that left the staged path (box did not fit, containment vote failed), per translation unit: dcp_debug_counters adds them up
+hipError_t read_lds_stats_unwarp(unsigned long long* out, bool reset);
+hipError_t read_lds_stats_stack(unsigned long long* out, bool reset);
 // -DDCP_DEBUG_BOUNDS builds: LDS taps outside their slab (count, first byte offset, slab bytes, site) per translation unit; zeros otherwise
 hipError_t read_bounds_unwarp(unsigned long long* out, bool reset);
+hipError_t read_bounds_stack(unsigned long long* out, bool reset);
 hipError_t read_bounds_color(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline(unsigned long long* out, bool reset);
 hipError_t read_bounds_spline_color(unsigned long long* out, bool reset);

@@ -567,6 +567,51 @@ def test_lds_staged_stack_kernel_and_its_fallbacks(hip, orc):
         hip.set_option("x_d_chunk", old[1])
 
 
+def test_counters_of_the_frame_and_the_stack_unit_are_summed_and_cleared_together(hip, orc):
+    """The frame kernels (unwarp_kernels.hip) and the stack kernels (stack_kernels.hip) each count the tiles that leave the staged path
+    in a __device__ pair of their own; dcp_debug_counters returns the sum and clears both.  One frame on remap_wg_kernel and one stack of
+    8 projections on stack_wg_kernel, each with a few tiles whose source box overflows the slab: kernel name, bit equality with the oracle
+    and the "box did not fit" count after each call, and (0, 0) on a second read after the reset.
+
+    The model: a 256 x 256 frame under list_fact = [1.5] is certified at level 1 only (level 2 also asks that at most 2 % of a lattice of
+    tiles overflow the slab, and under a uniform magnification every tile does), so neither call reaches these kernels.  Taken instead,
+    the nearest model that does: B(r) = 0.885 + 8.04e-5 r about the middle of a 512 x 2816 frame -- a minification at the centre that
+    grows into a 1.12 x magnification along x at the left and right ends, certified at level 2, where the tiles at both ends of the tile
+    rows 128..159 and 352..383 overflow the 144-element slab.  The stack call takes rows 128..191 (x_stack_wg = 2: stack_wg_kernel
+    also for a launch this small)."""
+    H, W, D = 512, 2816, 8
+    xc, yc, fact = 1407.5, 255.5, [0.885, 8.04e-5]
+    r0, nr = 128, 64
+    assert hip.tile_certificate(H, W, xc, yc, list_fact=fact) == 2
+    vol = noise(77, (D, H, W))
+    fa, nf = hip.fact_array(fact)
+    L = hip.lib()
+    src = hip.DeviceBuffer(vol.nbytes).upload(vol)
+    dst = hip.DeviceBuffer(vol.nbytes)
+    old = hip.get_option("x_stack_wg")
+    try:
+        hip.debug_counters()
+        hip.check(L.dcp_unwarp_image_f32(src.ptr, dst.ptr, H, W, W, 1, xc, yc, fa, nf, 1, 1, hip.BLEND_F64LERP, hip.MEM_DEVICE, -1, None))
+        assert hip.last_kernel() == "remap_wg_kernel<Radial,NF=2,f64lerp>"
+        assert np.array_equal(dst.download((D, H, W), np.float32)[0], orc.unwarp_image_backward(vol[0], xc, yc, fact, **kernel_oracle(orc, "f64lerp")))
+        # (the counts of both calls -- 4 workgroup tiles of the frame; 2 tiles x 2 depth chunks of the stack -- are what the library of
+        # the commit before the split, measured on an MI355X, returns for them)
+        assert hip.debug_counters() == (4, 0)
+        assert hip.debug_counters() == (0, 0)
+        hip.set_option("x_stack_wg", 2)
+        hip.check(L.dcp_unwarp_stack_rows_f32(src.ptr, dst.ptr, D, H, W, H * W, W, xc, yc, fa, nf, float(r0), nr, 1, hip.BLEND_F64LERP,
+                                              hip.MEM_DEVICE, -1, None))
+        assert hip.last_kernel() == "stack_wg_kernel<NF=4,f64lerp>"
+        assert np.array_equal(dst.download((D, nr, W), np.float32),
+                              orc.unwarp_stack_rows(vol, xc, yc, fact, r0, nr, coord_round_f32=True, **kernel_oracle(orc, "f64lerp")))
+        assert hip.debug_counters() == (4, 0)
+        assert hip.debug_counters() == (0, 0)
+    finally:
+        hip.set_option("x_stack_wg", old)
+        src.free()
+        dst.free()
+
+
 def test_host_stack_sharded_over_devices_of_one_process(hip, orc):
     """dcp_unwarp_stack_rows_multi_f32: depth shards on one worker thread per entry of `devices` (here the one GPU of
     the box, several times) give the same sinograms as one call; ragged and empty shards included."""

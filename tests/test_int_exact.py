@@ -1,5 +1,5 @@
 """8- / 16-bit integer data: tiles whose source box lies at coordinates >= 32 blend in the factorised form, which is exact there
-(every product and sum fits 53 bits: unwarp_kernels.hip, exact_lerp_pairs) and therefore equal to scipy's operation order bit for
+(every product and sum fits 53 bits: unwarp_device.h, exact_lerp_pairs) and therefore equal to scipy's operation order bit for
 bit.  Checked against the oracle (scipy's order everywhere) and against the same kernels with the option switched off.
 Reference behaviour: output dtype = input dtype, scipy's integer rounding (postprocessing.py:147, 251)."""
 import numpy as np
