@@ -120,6 +120,8 @@ SIGNATURES = {
     "dcp_window_slope_rows": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _vp]),
     "dcp_tilted_profiles_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _int, _int, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       _int, _int, _vp]),
+    "dcp_select_peaks_rows": (_int, [_vp, _int, _int, C.c_long, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _int, _int, _dbl, _int, _vp, _vp,
+                                     _int, _int, _vp]),
     "dcp_radon_2d": (_int, [_vp, _vp, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
     "dcp_radon_padded_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
     "dcp_nearest_sq_dists": (_int, [_vp, _vp, _int, _int, _int, _vp]),

@@ -1,7 +1,11 @@
-// api_profile.cpp -- dcp_local_extrema_rows, dcp_window_slope_rows and dcp_tilted_profiles_2d of the C ABI (include/discorpy_hip.h): plane
-// calls (api_plane.h) on a plane of profiles or on the image the profiles are taken from, their argument checks, the workspace of the
-// bands' coefficient planes (one lease of the spline workspace) and the launches of profile_kernels.hip.
+// api_profile.cpp -- dcp_local_extrema_rows, dcp_window_slope_rows, dcp_tilted_profiles_2d and dcp_select_peaks_rows of the C ABI
+// (include/discorpy_hip.h): plane calls (api_plane.h) on a plane of profiles or on the image the profiles are taken from, their argument
+// checks, the workspace of the bands' coefficient planes and of the peak tables (one lease of the spline workspace) and the launches of
+// profile_kernels.hip and select_peaks_kernels.hip.
 #include "api_plane.h"
+
+#include <cstring>
+#include <vector>
 
 using namespace dcpapi;
 
@@ -95,6 +99,56 @@ int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, lo
   t.dst = dst;
   t.out_bytes = out_bytes;
   return host_round_trip(t, c.stream, [&](const void* dsrc, void* ddst, void* dy, void* dx) { return launch(dsrc, ddst, (int64_t)c.W, dy, dx); });
+}
+
+int dcp_select_peaks_rows(const void* src, int nrows, int length, long src_row_stride, int dtype, const int32_t* peak_row, const int32_t* peak_index,
+                          int npeaks, int radius, double tol, int use_offset, unsigned char* keep, double* fit, int mem_kind, int device, void* stream) {
+  PlaneCall c;
+  int rc;
+  // (the outputs are not planes of the source's shape: checked here, and the round trip of host memory is this call's own)
+  if ((rc = make_plane_call(&c, src, nullptr, nrows, length, src_row_stride, dtype, 0, kPixelLimit, kReadsWindow, mem_kind, device, stream)) != DCP_OK)
+    return rc;
+  if ((rc = float_plane_only(dtype)) != DCP_OK) return rc;
+  if (!peak_row || !peak_index || !keep) return fail(DCP_ERR_INVALID_ARG, "null peak_row / peak_index / keep pointer");
+  if (npeaks < 1) return fail(DCP_ERR_INVALID_ARG, "npeaks must be at least 1 (got %d)", npeaks);
+  if (radius < 1) return fail(DCP_ERR_INVALID_ARG, "radius must be at least 1 (got %d)", radius);
+  if (radius > dcp::kSelectMaxRadius) return fail(DCP_ERR_UNSUPPORTED, "radius above %d (got %d)", dcp::kSelectMaxRadius, radius);
+  if (tol != tol) return fail(DCP_ERR_INVALID_ARG, "tol is NaN");
+  if (use_offset != 0 && use_offset != 1) return fail(DCP_ERR_INVALID_ARG, "use_offset must be 0 or 1 (got %d)", use_offset);
+  for (int k = 0; k < npeaks; ++k)
+    if (peak_row[k] < 0 || peak_row[k] >= nrows || peak_index[k] < 0 || peak_index[k] >= length)
+      return fail(DCP_ERR_INVALID_ARG, "peak %d: row %d, index %d lies outside the %d x %d plane", k, peak_row[k], peak_index[k], nrows, length);
+  const size_t keep_bytes = (size_t)npeaks, fit_bytes = (size_t)npeaks * 6 * sizeof(double);
+  {
+    const char *s0 = (const char*)src, *s1 = s0 + ((size_t)(nrows - 1) * (size_t)src_row_stride + (size_t)length) * c.esz;
+    const char *k0 = (const char*)keep, *k1 = k0 + keep_bytes;
+    const char *f0 = (const char*)fit, *f1 = f0 + fit_bytes;
+    if ((s0 < k1 && k0 < s1) || (fit && s0 < f1 && f0 < s1)) return fail(DCP_ERR_INVALID_ARG, "src and keep / fit overlap: %s", kReadsWindow);
+    if (fit && k0 < f1 && f0 < k1) return fail(DCP_ERR_INVALID_ARG, "keep and fit overlap");
+  }
+  PlaneDevice on(c.device);
+  if (on.rc != DCP_OK) return on.rc;
+  WorkspaceLease lease;
+  if ((rc = lease.acquire(dcp::select_peaks_work_bytes(npeaks), c.stream)) != DCP_OK) return rc;
+  auto launch = [&](const void* s, int64_t rs, unsigned char* k, double* f) {
+    return dcp::launch_select_peaks(s, nrows, length, rs, dtype, peak_row, peak_index, npeaks, radius, tol, use_offset != 0, k, f, lease.buf, c.stream);
+  };
+  if (!c.host) {
+    DCP_HIP(launch(c.src, c.rs, keep, fit));
+    return DCP_OK;
+  }
+  // host memory: both outputs come back in one block, the fit rows (8-byte aligned) in front of the keep bytes
+  std::vector<unsigned char> back(fit_bytes + keep_bytes);
+  HostTrip t = packed_rows(c);
+  t.dst = back.data();
+  t.out_bytes = back.size();
+  rc = host_round_trip(t, c.stream, [&](const void* dsrc, void* ddst, void*, void*) {
+    return launch(dsrc, (int64_t)c.W, static_cast<unsigned char*>(ddst) + fit_bytes, static_cast<double*>(ddst));
+  });
+  if (rc != DCP_OK) return rc;
+  memcpy(keep, back.data() + fit_bytes, keep_bytes);
+  if (fit) memcpy(fit, back.data(), fit_bytes);
+  return DCP_OK;
 }
 
 }  // extern "C"

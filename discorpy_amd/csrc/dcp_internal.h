@@ -324,6 +324,24 @@ size_t profile_band_elems(int H, int W, bool vertical, int n);
 hipError_t launch_tilted_profiles(const void* src, void* dst, int H, int W, int64_t src_stride, int dtype, bool vertical, int nprof, int len,
                                   const double* ycoord, const double* xcoord, const int32_t* band_lo, const int32_t* band_n, void* work, size_t work_bytes,
                                   hipStream_t stream);
+// select_peaks_kernels.hip: select_good_peaks on `npeaks` candidates of an (N, L) plane of kF32 / kF64 profiles: candidate k is sample
+// peak_idx[k] of row peak_row[k] (HOST arrays, every entry inside the plane).  keep[k] = 1 where the fit of the window of `radius`
+// samples on either side succeeded with |c| < radius / 2, the 80th percentile of |fit - y| below tol and (use_offset) |d| < tol;
+// fit (may be null): per candidate a, b, c, d, that percentile and the status below.  keep and fit are device memory.  `work`:
+// select_peaks_work_bytes(npeaks) of device memory.  THE STREAM IS SYNCHRONISED once, after the two tables have been copied.
+constexpr int kSelectMaxRadius = 128;          // the window of one wave: 257 doubles of LDS
+enum FitStatus : int {
+  kFitOk = 0,
+  kFitShort = 1,          // a window of 3 samples or fewer: no fit
+  kFitNotFinite = 2,      // a NaN or an infinity in the window: no fit
+  kFitConstant = 3,       // max == min: no fit
+  kFitBudget = 4,         // the evaluations ran out before a stopping rule held
+  kFitDiverged = 5,       // a sum, a step or a parameter stopped being finite
+  kFitGradient = 6        // the residuals at right angles to the Jacobian's columns to machine precision before a stopping rule held
+};
+inline size_t select_peaks_work_bytes(int npeaks) { return (size_t)npeaks * 2 * sizeof(int32_t); }
+hipError_t launch_select_peaks(const void* src, int N, int L, int64_t src_stride, int dtype, const int32_t* peak_row, const int32_t* peak_idx, int npeaks,
+                               int radius, double tol, bool use_offset, unsigned char* keep, double* fit, void* work, hipStream_t stream);
 // radon_kernels.hip: the sinogram of the N x N plane at src (kF32 / kF64, rows `src_stride` elements apart) for `nangles` angles, as
 // DESIGN.md ("Radon transform") defines it: the plane zeroed outside its inscribed circle, rotated about (N / 2, N / 2) by bilinear
 // interpolation with zeros outside, and summed over the rows in ascending order, all in float64.  table: HOST array of {cos a, sin a,

@@ -39,9 +39,15 @@ quotient are evaluated in the profile's own type as NumPy 2 evaluates them.
 
 These names are listed in :data:`RADON`.
 
-Out of scope: the selection of good peaks behind the peak search (``select_good_peaks``: a scipy ``curve_fit`` per peak), so
-``select_peaks=True`` raises ``NotImplementedError`` in the peak search and in the Radon slope functions alike, and ``circle=False`` of
-the Radon transform, which raises too.
+* :func:`select_good_peaks`   reference ``linepattern.py:75-152``: same name, arguments and defaults, on one profile or on an (N, L)
+  batch of profiles with their candidate peaks: one Gaussian fit per candidate, one wave of the GPU per fit (``dcp_select_peaks_rows``;
+  the kernel is in ``csrc/select_peaks_kernels.hip``; ``DESIGN.md``, "Peak selection")
+
+This name is listed in :data:`PEAK_SELECTION`.
+
+Out of scope: the ``select_peaks`` flag, which is not wired to :func:`select_good_peaks` yet, so ``select_peaks=True`` still raises
+``NotImplementedError`` in the peak search, in the cross-point functions and in the Radon slope functions alike (the docstring of
+:func:`select_good_peaks` shows the composition that works today), and ``circle=False`` of the Radon transform, which raises too.
 
 The Gaussian runs as hand-written HIP kernels through ``dcp_correlate_sym_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/gauss_kernels.hip``) with scipy's arithmetic restated operation by operation (``DESIGN.md``), so the result equals scipy's bit
@@ -70,6 +76,9 @@ RADON_MAX_SIDE, RADON_MAX_ANGLES = 32768, 65535       # dcp_radon_2d: every inde
 CROSS_POINTS = ["get_tilted_profiles", "sliding_window_slope", "locate_subpixel_point", "get_local_extrema_points",
                 "get_cross_points_hor_lines", "get_cross_points_ver_lines"]
 PEAK_MAX_RADIUS = 128          # dcp_local_extrema_rows: the sorted tail stays inside one block of NumPy's pairwise sum
+# the selection of good peaks behind the peak search
+PEAK_SELECTION = ["select_good_peaks"]
+SELECT_MAX_RADIUS = 128        # dcp_select_peaks_rows: the window of one wave, 257 doubles of LDS
 
 
 def _gaussian_weights(sigma, truncate=4.0, radius=None):
@@ -554,6 +563,88 @@ def get_local_extrema_points(list_data, option="min", radius=7, sensitive=0.1, d
                 results.append(np.asarray([i - 1 + locate_subpixel_point(rows[p, i - 1:i + 2], option="min") for i in found[p, :count].astype(np.int64)]))
         else:
             results.append(found[p, :count].astype(np.int64))
+    return results[0] if single else results
+
+
+def select_good_peaks(list_data, peaks, tol=0.2, radius=11, sigma=0, use_offset=True):
+    """
+    Select good peaks from the input data based on Gaussian fitting and tolerance criteria (reference ``linepattern.py:105-152``),
+    on one profile or on every row of a batch: one wave of the GPU per candidate (``dcp_select_peaks_rows``).
+
+    Parameters
+    ----------
+    list_data : array_like
+        1d-array, or an (N, L) batch of them.  float32 / float64; other types are read as float64 before everything (scipy would
+        smooth an integer profile in its own type).
+    peaks : list of int
+        Indices of candidate peaks in the data.  For a batch: a list of N such lists, one per row.
+    tol : float, optional
+        Tolerance for peak fitting accuracy.
+    radius : int, optional
+        Radius around each peak to consider for fitting.  At most 128.
+    sigma : float, optional
+        Standard deviation for Gaussian smoothing: this module's :func:`gaussian_filter` along the rows.
+    use_offset : bool, optional
+        Use fitted offset value for judging if True.
+
+    Returns
+    -------
+    list of int
+        Indices of the selected good peaks, as an array in the order given (``np.asarray([])`` where none is selected, as in the
+        reference).  For a batch: a list of N such arrays.
+
+    Notes
+    -----
+    The fit restates the Levenberg-Marquardt iteration scipy's ``curve_fit`` runs for the reference (``DESIGN.md``, "Peak
+    selection"); the decisions are the reference's wherever its own fit does not hang on where the iteration stops.  A constant
+    window is rejected by ``max == min``, where the reference tests ``np.std(...) != 0.0``.
+
+    ``select_peaks=True`` of the peak search is not wired to this function yet.  The composition that works today, on data the
+    caller has prepared (``denoise=False, norm=False``)::
+
+        points = get_local_extrema_points(d, option="min", radius=r, denoise=False, norm=False, subpixel=False)
+        points = select_good_peaks(np.max(d) - d, points, radius=r)
+        points = [p - 1 + locate_subpixel_point(d[p - 1:p + 2], option="min") for p in points]
+    """
+    rows, single = _profile_rows(list_data, "select_good_peaks")
+    nrows, num_point = rows.shape
+    radius = int(radius)
+    if radius < 1:
+        raise ValueError("select_good_peaks: radius must be at least 1 (got %d)" % radius)
+    if radius > SELECT_MAX_RADIUS:
+        raise NotImplementedError("select_good_peaks: a radius above %d is not implemented on the GPU path (got %d)" % (SELECT_MAX_RADIUS, radius))
+    tol = float(tol)
+    if tol != tol:
+        raise ValueError("select_good_peaks: tol is NaN")
+    per_row = [peaks] if single else list(peaks)
+    if len(per_row) != nrows:
+        raise ValueError("select_good_peaks: %d rows but %d lists of peaks" % (nrows, len(per_row)))
+    per_row = [np.asarray(p) for p in per_row]
+    for k, p in enumerate(per_row):
+        if p.ndim != 1 or (p.size and p.dtype.kind not in "iu"):
+            raise ValueError("select_good_peaks: the peaks of a row are a 1D sequence of integers")
+        if p.size and (p.min() < 0 or p.max() >= num_point):
+            raise ValueError("select_good_peaks: row %d has a peak outside [0, %d)" % (k, num_point))
+    counts = [p.size for p in per_row]
+    npeaks = int(sum(counts))
+    if npeaks == 0:
+        return np.asarray([]) if single else [np.asarray([]) for _ in range(nrows)]
+    if sigma > 0:
+        rows = gaussian_filter(rows, (0, sigma))
+    peak_row = np.repeat(np.arange(nrows, dtype=np.int32), counts)
+    peak_idx = np.concatenate(per_row).astype(np.int32)
+    keep = np.zeros(npeaks, np.uint8)
+    F.require_device()
+    img = _rows_image(rows)
+    i32p = F.C.POINTER(F.C.c_int32)
+    F.check(F.lib().dcp_select_peaks_rows(img.ptr, nrows, num_point, _row_stride(img), img.code, peak_row.ctypes.data_as(i32p),
+                                          peak_idx.ctypes.data_as(i32p), npeaks, radius, tol, 1 if use_offset else 0, keep.ctypes.data, None,
+                                          img.mem, img.device, img.stream))
+    results, first = [], 0
+    for p, count in zip(per_row, counts):
+        good = p[keep[first:first + count] != 0]
+        results.append(good if good.size else np.asarray([]))
+        first += count
     return results[0] if single else results
 
 

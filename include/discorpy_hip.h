@@ -675,6 +675,32 @@ int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, lo
                            int length, const double* ycoords, const double* xcoords, const int32_t* band_lo, const int32_t* band_count,
                            int mem_kind, int device, void* stream);
 
+/* ---- the selection of good peaks behind the peak search (discorpy/prep/linepattern.py:75-152) ----
+ * dcp_select_peaks_rows: select_good_peaks (after its smoothing step) on `npeaks` candidate peaks of a plane of profiles as
+ * dcp_local_extrema_rows takes it (`nrows` rows of `length` samples, DCP_DTYPE_FLOAT32 / FLOAT64, rows `src_row_stride` elements
+ * apart, the mem_kind / device / stream triple of dcp_label_2d).  Candidate k is sample peak_index[k] of row peak_row[k]: two HOST
+ * int32 arrays.  One wave per candidate, everything in double:
+ *   window   w = row[start .. stop), start = max(0, p - radius), stop = min(length, p + radius + 1), n = stop - start;
+ *   no fit   for n <= 3 (status 1), a NaN or an infinity in the window (status 2) and max(w) == min(w) (status 3; the reference tests
+ *            np.std(w) != 0.0, which on a constant window hangs on the rounding of np.mean);
+ *   y        = (w - min(w)) / std(w), the population standard deviation; x_i = i - n / 2 (integer division);
+ *   fit      a exp(-((x - c) / (2 b^2))^2) + d to (x, y) from (a, b, c, d) = (1, 1, 0, 0) by the Levenberg-Marquardt iteration of MINPACK's
+ *            lmdif as scipy.optimize.curve_fit runs it by default: forward-difference Jacobian (relative step 2^-26), columns scaled by
+ *            the running maximum of their norms, a trust region of 100 |D x| at first, stop on the relative decrease of the cost
+ *            (actual and predicted) or on the trust region against |D x|, both at 1.49012e-8, at most 1000 evaluations of the model
+ *            (a Jacobian counts 4).  A fit that runs out of them (status 4), whose sums, step or parameters stop being finite (status 5)
+ *            or whose residuals stand at right angles to the Jacobian's columns to 2^-52 first (status 6) has failed;
+ *   num      = np.percentile(|fit - y|, 80): linear interpolation at 0.8 (n - 1) of the sorted values;
+ *   keep[k]  = 1 iff status 0 and |c| < radius / 2 (integer division) and num < tol and (use_offset == 0 or |d| < tol), else 0.
+ * The sums of a fit are reduced across the wave in a fixed order: a candidate's result does not depend on the others of the call.
+ * keep: npeaks bytes; fit: npeaks x 6 doubles (a, b, c, d, num, status; NaN for what was not computed), or null.  Both live where the
+ * plane lives.  A null pointer other than fit, nrows, length or npeaks below 1, a stride below the length, a candidate outside the
+ * plane, radius below 1, a NaN tol, use_offset other than 0 or 1, an unknown dtype or mem_kind and src overlapping keep or fit are
+ * DCP_ERR_INVALID_ARG; radius above 128 and other dtypes are DCP_ERR_UNSUPPORTED; all before any device call.  For DCP_MEM_DEVICE the call
+ * synchronises `stream` once (the two tables are copied from host memory). */
+int dcp_select_peaks_rows(const void* src, int nrows, int length, long src_row_stride, int dtype, const int32_t* peak_row, const int32_t* peak_index,
+                          int npeaks, int radius, double tol, int use_offset, unsigned char* keep, double* fit, int mem_kind, int device, void* stream);
+
 /* ---- the Radon transform behind the slope search of the line-pattern route (discorpy/prep/linepattern.py:302-449) ----
  * dcp_radon_2d: the sinogram of a side x side plane (DCP_DTYPE_FLOAT32 / FLOAT64, rows `src_row_stride` elements apart, read in place)
  * for `nangles` angles in one launch; dst: (side, nangles) doubles, row-major.  With c0 = side / 2 (integer division):

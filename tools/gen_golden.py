@@ -503,6 +503,171 @@ if "--g31" in sys.argv[1:]:
     raise SystemExit(0)
 
 
+# ---- G32: select_good_peaks of discorpy.prep.linepattern (skimage stubbed as for G26-G31).  Cases of small profiles with candidate peaks
+# and the arguments; per peak, for the float64 rows and for the same rows as float32: the reference's decision with and without
+# use_offset (select_good_peaks on that one peak), the reference's four values (check, c, d, num) read through _get_gauss_peak_fit and the
+# lines of select_good_peaks, and the same four from a refit with curve_fit's tolerances at 1e-14 and maxfev 20000.  delta = 4 x the 99th
+# percentile, over the peaks where both fits succeed and differ by less than 0.05 in each quantity, of the largest difference among
+# (c, d, num) between the two fits: the reference's own sensitivity to where its iteration stops.  A peak is CLEAR when the two fits give
+# the same decision and, wherever a fit succeeded, | |c| - radius // 2 |, |num - tol| and (use_offset) | |d| - tol | are at least delta.
+# Runs alone as   python tools/gen_golden.py --g32
+G32_RADII = (3, 7, 11)
+G32_HOPELESS_RADII = (3, 7)      # the noise row, the ramp and the square wave
+G32_TOL = 0.2
+G32_MAX_UNCLEAR = 0.15
+G32_MIN_PER_CLASS = 20
+G32_CLASSES = ("kept", "shift", "percentile", "offset", "raised")
+
+
+def g32_rows():
+    """(rows (27, 160), candidates per row): 6 kinds of line rows x 4 noise strengths, then a noise row, a ramp and a square wave."""
+    rng = np.random.default_rng(32)
+    x = np.arange(160.0)
+    centres = np.arange(14.0, 150.0, 21.0) + np.array([0.0, 0.3, -0.4, 0.2, 0.45, -0.25, 0.1])
+
+    def bumps(width, heights, base):
+        return base + sum(h * np.exp(-0.5 * ((x - c) / width) ** 2) for c, h in zip(centres, heights))
+    h_even = np.array([1.0, 0.8, 1.2, 0.6, 1.0, 0.9, 1.1])
+    kinds = [bumps(1.0, h_even, 0.1), bumps(1.6, h_even[::-1], 0.3), bumps(2.4, h_even, 0.0), bumps(3.4, 0.7 * h_even, 0.5),
+             # one shoulder on every line: a second, lower line 4 samples to the right
+             bumps(1.5, h_even, 0.2) + sum(0.45 * h * np.exp(-0.5 * ((x - c - 4.0) / 1.5) ** 2) for c, h in zip(centres, h_even)),
+             # flat-topped bumps: a line clipped at 55 % of its height
+             np.minimum(bumps(2.5, np.ones(7), 0.0), 0.55) + 0.1]
+    rows, cands = [], []
+    for kind in kinds:
+        for noise in (0.0, 0.01, 0.03, 0.08):
+            rows.append(kind + noise * rng.standard_normal(160))
+            on = np.round(centres).astype(np.int64)
+            cands.append(np.concatenate((on, on - 1, on[::2] + 2, on[1::2] - 4, on[1::2] + 1)))
+    every9 = np.arange(0, 160, 9)
+    rows += [0.5 + 0.2 * rng.standard_normal(160), 0.01 * x + 0.25, ((x // 20) % 2).astype(np.float64)]
+    cands += [every9, every9, every9]
+    return np.asarray(rows), cands
+
+
+def g32():
+    import functools
+    import types
+    import warnings
+    from scipy.optimize import curve_fit
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    for mod, attr in (("skimage.filters", "threshold_otsu"), ("skimage.segmentation", "clear_border"), ("skimage.transform", "radon")):
+        if not hasattr(sys.modules[mod], attr):
+            setattr(sys.modules[mod], attr, None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import discorpy.prep.linepattern as rlp
+    tight_fit = functools.partial(curve_fit, ftol=1e-14, xtol=1e-14, gtol=1e-14, maxfev=20000)
+
+    def four(list_data, p, radius):
+        """(check, c, d, num) of one peak: the lines of the reference's select_good_peaks around its own _get_gauss_peak_fit."""
+        start, stop = max(0, p - radius), min(len(list_data), p + radius + 1)
+        if stop - start <= 3:
+            return [0.0, np.nan, np.nan, np.nan]
+        list_sub = list_data[start:stop]
+        std = np.std(list_sub)
+        if std == 0.0:
+            return [0.0, np.nan, np.nan, np.nan]
+        list_norm = (list_sub - np.min(list_sub)) / std
+        fit_data, del_x, offset, check = rlp._get_gauss_peak_fit(list_norm)
+        return [float(check), float(del_x), float(offset), float(np.percentile(np.abs(fit_data - list_norm), 80))]
+
+    def decide(v, radius, tol, use_offset):
+        return bool(v[0]) and abs(v[1]) < radius // 2 and v[3] < tol and (not use_offset or abs(v[2]) < tol)
+
+    rows, cands = g32_rows()
+    # one row of 600 samples for radius 128: three wide lines, a little noise
+    xb = np.arange(600.0)
+    big = 0.2 + sum(h * np.exp(-0.5 * ((xb - c) / w) ** 2) for c, h, w in ((130.3, 1.0, 18.0), (300.0, 0.8, 26.0), (470.6, 1.2, 12.0)))
+    big = big + 0.01 * np.random.default_rng(33).standard_normal(600)
+    vec1 = np.array([0, 1.5, 5, 1.5, 0, 0, 3, 10, 3, 0])                       # the reference's two test vectors (test_linepattern.py:53-67)
+    vec2 = np.array([0, 1, 2, 9, 2, 1, 0, 0, 3, 10, 3, 0, 0], np.float64)      # (an integer array there: scipy smooths it in its own type)
+    # (name, rows, candidates per row, radius, tol, sigma)
+    cases = [("r%d" % r, rows[:24], cands[:24], r, G32_TOL, 0.0) for r in G32_RADII]
+    cases += [("h%d" % r, rows[24:], cands[24:], r, G32_TOL, 0.0) for r in G32_HOPELESS_RADII]
+    cases.append(("big", big[None, :], [np.array([130, 300, 471, 120, 310, 480, 70, 215, 385, 560, 128, 129, 299, 301, 470, 472])], 128, G32_TOL, 0.0))
+    cases.append(("vec1", vec1[None, :], [np.array([2, 7])], 3, 0.1, 0.0))
+    cases.append(("vec2", vec2[None, :], [np.array([3, 9])], 3, 0.3, 1.0))
+    cases.append(("smooth", rows[[3, 7, 11, 19, 22]], [cands[k] for k in (3, 7, 11, 19, 22)], 7, G32_TOL, 1.5))
+    out = dict(case_names=np.array([c[0] for c in cases]), radius=np.array([c[3] for c in cases], np.int64), tol=f64([c[4] for c in cases]),
+               sigma=f64([c[5] for c in cases]))
+    measured = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for name, crow, ccand, radius, tol, sigma in cases:
+            out[name + "_rows"] = f64(crow)
+            out[name + "_row_of"] = np.concatenate([np.full(len(c), k, np.int32) for k, c in enumerate(ccand)])
+            out[name + "_idx"] = np.concatenate(ccand).astype(np.int32)
+            for dt in ("float64", "float32"):
+                ref, tight, keep = [], [], []
+                for k, peaks in enumerate(ccand):
+                    data = crow[k].astype(dt)
+                    smooth = ndi.gaussian_filter1d(data, sigma) if sigma > 0 else data
+                    for p in peaks:
+                        p = int(p)
+                        ref.append(four(smooth, p, radius))
+                        rlp.curve_fit = tight_fit
+                        try:
+                            tight.append(four(smooth, p, radius))
+                        finally:
+                            rlp.curve_fit = curve_fit
+                        keep.append([len(rlp.select_good_peaks(data, [p], tol=tol, radius=radius, sigma=sigma, use_offset=uo)) == 1 for uo in (True, False)])
+                        assert keep[-1] == [decide(ref[-1], radius, tol, uo) for uo in (True, False)]
+                measured[name, dt] = (f64(ref), f64(tight), np.array(keep))
+    # delta: over every case and both element types
+    diffs = []
+    for ref, tight, _ in measured.values():
+        both = (ref[:, 0] == 1) & (tight[:, 0] == 1)
+        d = np.abs(ref[both, 1:] - tight[both, 1:])
+        diffs.append(d[(d < 0.05).all(axis=1)].max(axis=1))
+    p99 = float(np.percentile(np.concatenate(diffs), 99))
+    delta = 4.0 * p99
+    out["p99"], out["delta"] = np.float64(p99), np.float64(delta)
+    total, unclear = 0, 0
+    counts = dict.fromkeys(G32_CLASSES, 0)
+    for (name, dt), (ref, tight, keep) in measured.items():
+        radius, tol = int(out["radius"][list(out["case_names"]).index(name)]), float(out["tol"][list(out["case_names"]).index(name)])
+        clear = np.empty((len(ref), 2), bool)
+        for i in range(len(ref)):
+            for j, uo in enumerate((True, False)):
+                ok = decide(ref[i], radius, tol, uo) == decide(tight[i], radius, tol, uo)
+                for v in (ref[i], tight[i]):
+                    if v[0] == 1:
+                        margins = [abs(abs(v[1]) - radius // 2), abs(v[3] - tol)] + ([abs(abs(v[2]) - tol)] if uo else [])
+                        ok = ok and min(margins) >= delta
+                clear[i, j] = ok
+            if clear[i, 0]:
+                v, t = ref[i], tight[i]
+                if keep[i, 0]:
+                    counts["kept"] += 1
+                elif v[0] == 0 and np.isfinite(v[3]):                     # (the fit raised -- not a window rejected before any fit)
+                    counts["raised"] += 1
+                elif v[0] == 1 and abs(v[1]) >= radius // 2:
+                    counts["shift"] += 1
+                elif v[0] == 1 and v[3] >= tol:
+                    counts["percentile"] += 1
+                elif v[0] == 1:
+                    counts["offset"] += 1
+        key = "%s_%s_" % (name, "f64" if dt == "float64" else "f32")
+        out[key + "ref"], out[key + "tight"], out[key + "keep"], out[key + "clear"] = ref, tight, keep, clear
+        total += clear.size
+        unclear += int((~clear).sum())
+        print("g32 %-7s %-7s peaks %4d kept %4d / %4d clear %4d / %4d" % (name, dt, len(ref), keep[:, 0].sum(), keep[:, 1].sum(), clear[:, 0].sum(),
+                                                                       clear[:, 1].sum()))
+    out["unclear_share"] = np.float64(unclear / total)
+    print("g32 p99 %.4g delta %.4g unclear %.2f %% classes %s" % (p99, delta, 100.0 * unclear / total, counts))
+    assert unclear <= G32_MAX_UNCLEAR * total, (unclear, total)
+    assert min(counts.values()) >= G32_MIN_PER_CLASS, counts
+    save("g32_select_peaks", **out)
+    assert os.path.getsize(os.path.join(OUT, "g32_select_peaks.npz")) <= 400 << 10
+
+
+if "--g32" in sys.argv[1:]:
+    g32()
+    raise SystemExit(0)
+
+
 # ---- G1: the reference's own unwarp_image_backward test input (tests/test_postprocessing.py:77-85)
 hei = wid = 64
 mat = np.zeros((hei, wid), dtype=np.float32)
@@ -1684,4 +1849,5 @@ g28()
 g29()
 g30()
 g31()
+g32()
 print("done")

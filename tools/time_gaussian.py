@@ -52,6 +52,16 @@ calls of a sweep give the same bits.  There is no time to beat: the numbers go t
 patch of the source staged in LDS is worth its code.
 
     python tools/time_gaussian.py --radon [--side 600] [--angles 61] [--dtypes float32,float64] [--rounds 5] [--reps 200]
+
+--select-peaks: the selection behind the peak search, with options of its own.  Time dcp_select_peaks_rows (one launch of
+select_peaks_kernel, a wave per candidate) on 4096 candidates at radius 11 on device-resident float32 and float64 profiles of 2000
+samples: lines 90 apart on a sloping background with noise, three candidates in four on a line, the fourth between two lines.  Warm-up
+calls, then `--rounds` (at least five) rounds of `--reps` back-to-back calls between device events.  A call copies its two candidate
+tables from host memory and waits for that copy, so the same call on one candidate is timed beside it as the floor of a call.  Printed
+in ms per call: the median round with its range, the floor, how many candidates were kept, how many ended with each status, and whether
+two calls give the same bits.  There is no time to beat: the numbers go to DESIGN.md as they are.
+
+    python tools/time_gaussian.py --select-peaks [--peaks 4096] [--radius 11] [--length 2000] [--dtypes float32,float64] [--rounds 5] [--reps 20]
 """
 import argparse
 import os
@@ -73,7 +83,9 @@ def main():
         return cross_points_main([v for v in sys.argv[1:] if v != "--cross-points"])
     if "--radon" in sys.argv[1:]:
         return radon_main([v for v in sys.argv[1:] if v != "--radon"])
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    if "--select-peaks" in sys.argv[1:]:
+        return select_peaks_main([v for v in sys.argv[1:] if v != "--select-peaks"])
+    ap =argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sides", default="2048,4096")
     ap.add_argument("--dtypes", default="float32,uint16")
     ap.add_argument("--sigmas", default="3,10")
@@ -414,6 +426,84 @@ def radon_main(argv):
             dt.name, med["floor"], min(rounds["floor"]), max(rounds["floor"]), nang))
         print("%-8s ratio 90 / 0       %8.3f of the calls, %.3f less the floor  [%s]" % (
             dt.name, med["90"] / med["0"], (med["90"] - med["floor"]) / (med["0"] - med["floor"]), kernel), flush=True)
+    return 0
+
+
+def select_peaks_main(argv):
+    ap = argparse.ArgumentParser(prog="time_gaussian.py --select-peaks", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--peaks", type=int, default=4096)
+    ap.add_argument("--radius", type=int, default=11)
+    ap.add_argument("--length", type=int, default=2000)
+    ap.add_argument("--dtypes", default="float32,float64")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args(argv)
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    from discorpy_amd import _ffi as F
+    L = F.lib()
+    F.require_device()
+    dev, length, radius = -1, a.length, a.radius
+    i32p = F.C.POINTER(F.C.c_int32)
+    rng = np.random.default_rng(12)
+    # profiles of a line pattern as the cross-point route hands them on: lines 90 apart, of width 4, on a sloping background, with noise;
+    # three candidates in four on a line's centre, the fourth half-way between two lines (a false peak)
+    per_row = (length - 90) // 90
+    nrows = -(-a.peaks // per_row)
+    x = np.arange(length, dtype=np.float64)
+    rows = np.empty((nrows, length))
+    peak_row, peak_idx = [], []
+    for r in range(nrows):
+        centres = 45.0 + 90.0 * np.arange(per_row) + rng.uniform(-3.0, 3.0, per_row)
+        rows[r] = 0.2 + 1e-4 * x + np.exp(-0.5 * ((x[:, None] - centres[None, :]) / 4.0) ** 2).sum(axis=1) + 0.02 * rng.standard_normal(length)
+        at = np.round(centres).astype(np.int32)
+        at[3::4] += 45
+        peak_row.append(np.full(per_row, r, np.int32))
+        peak_idx.append(np.clip(at, 0, length - 1))
+    peak_row, peak_idx = np.concatenate(peak_row)[:a.peaks], np.concatenate(peak_idx)[:a.peaks]
+    npeaks = len(peak_idx)
+    print("select_good_peaks: %d candidates at radius %d on %d x %d device-resident profiles, %d rounds of %d calls, ms per call" % (
+        npeaks, radius, nrows, length, a.rounds, a.reps))
+    for name in a.dtypes.split(","):
+        dt = np.dtype(name)
+        code = F.DTYPE_BY_NAME[dt.name]
+        src = F.DeviceBuffer(nrows * length * dt.itemsize, dev).upload(rows.astype(dt))
+        keep, fit = F.DeviceBuffer(npeaks, dev), F.DeviceBuffer(npeaks * 48, dev)
+
+        def run(count):
+            F.check(L.dcp_select_peaks_rows(src.ptr, nrows, length, length, code, peak_row.ctypes.data_as(i32p), peak_idx.ctypes.data_as(i32p), count,
+                                            radius, 0.2, 1, keep.ptr, fit.ptr, F.MEM_DEVICE, dev, None))
+
+        def timed(count):
+            e0, e1 = F.Event(dev), F.Event(dev)
+            e0.record()
+            for _r in range(a.reps):
+                run(count)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_ms(e1) / a.reps
+        for _ in range(a.warmup):
+            run(npeaks)
+        first = fit.download((npeaks, 6), np.float64)
+        run(npeaks)
+        again = fit.download((npeaks, 6), np.float64)
+        kept = keep.download((npeaks,), np.uint8)
+        kernel = F.last_kernel()
+        for _ in range(a.warmup):
+            run(1)
+        F.check(L.dcp_stream_synchronize(dev, None))
+        rounds = {npeaks: [], 1: []}
+        for _ in range(a.rounds):
+            for count in (npeaks, 1):
+                rounds[count].append(timed(count))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        status = first[:, 5].astype(np.int64)
+        print("%-8s %d candidates    %8.4f ms (rounds %.4f .. %.4f)  less the floor %8.4f ms  kept %d, status counts %s, two calls equal: %s" % (
+            dt.name, npeaks, med[npeaks], min(rounds[npeaks]), max(rounds[npeaks]), med[npeaks] - med[1], int(kept.sum()),
+            np.bincount(status, minlength=7).tolist(), np.array_equal(first, again, equal_nan=True)), flush=True)
+        print("%-8s floor of a call    %8.4f ms (rounds %.4f .. %.4f)  [one candidate: the tables' copy, the wait for it, one launch]  [%s]" % (
+            dt.name, med[1], min(rounds[1]), max(rounds[1]), kernel), flush=True)
     return 0
 
 
