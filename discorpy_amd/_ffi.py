@@ -122,6 +122,7 @@ SIGNATURES = {
                                       _int, _int, _vp]),
     "dcp_select_peaks_rows": (_int, [_vp, _int, _int, C.c_long, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _int, _int, _dbl, _int, _vp, _vp,
                                      _int, _int, _vp]),
+    "dcp_extrema_select_rows": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _dbl, _int, _vp, C.c_long, _dbl, _int, _vp, _vp, _int, _int, _vp]),
     "dcp_radon_2d": (_int, [_vp, _vp, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
     "dcp_radon_padded_2d": (_int, [_vp, _vp, _int, _int, C.c_long, _int, _int, _dp, _int, _int, _vp]),
     "dcp_nearest_sq_dists": (_int, [_vp, _vp, _int, _int, _int, _vp]),

@@ -764,9 +764,10 @@ int dcp_debug_bounds(uint64_t* out, int n, int reset) {
 #endif
   out[0] = out[1] = out[2] = out[3] = 0;
   DCP_HIP(hipDeviceSynchronize());
-  hipError_t (*readers[10])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_stack, dcp::read_bounds_color, dcp::read_bounds_spline,
+  hipError_t (*readers[12])(unsigned long long*, bool) = {dcp::read_bounds_unwarp, dcp::read_bounds_stack, dcp::read_bounds_color, dcp::read_bounds_spline,
                                                            dcp::read_bounds_spline_color, dcp::read_bounds_spline_frames, dcp::read_bounds_gauss, dcp::read_bounds_label,
-                                                           dcp::read_bounds_fourier, dcp::read_bounds_profile};
+                                                           dcp::read_bounds_fourier, dcp::read_bounds_profile, dcp::read_bounds_select,
+                                                           dcp::read_bounds_extrema_select};
   for (auto rd : readers) {
     unsigned long long v[4];
     DCP_HIP(rd(v, reset != 0));

@@ -5,6 +5,8 @@
 #include "api_plane.h"
 
 #include <cstring>
+#include <memory>
+#include <new>
 #include <vector>
 
 using namespace dcpapi;
@@ -148,6 +150,95 @@ int dcp_select_peaks_rows(const void* src, int nrows, int length, long src_row_s
   if (rc != DCP_OK) return rc;
   memcpy(keep, back.data() + fit_bytes, keep_bytes);
   if (fit) memcpy(fit, back.data(), fit_bytes);
+  return DCP_OK;
+}
+
+int dcp_extrema_select_rows(const void* src, double* dst, int nrows, int length, long src_row_stride, int dtype, int radius, double sensitive,
+                            int subpixel, const void* sel, long sel_row_stride, double tol, int use_offset, double* cand, unsigned char* keep,
+                            int mem_kind, int device, void* stream) {
+  PlaneCall c;
+  int rc;
+  if ((rc = make_plane_call(&c, src, dst, nrows, length, src_row_stride, dtype, sizeof(double), kPixelLimit, kReadsWindow, mem_kind, device, stream)) != DCP_OK)
+    return rc;
+  if ((rc = float_plane_only(dtype)) != DCP_OK) return rc;
+  if (sel && (rc = check_row_stride("sel_row_stride", sel_row_stride, length)) != DCP_OK) return rc;
+  if (radius < 1) return fail(DCP_ERR_INVALID_ARG, "radius must be at least 1 (got %d)", radius);
+  if (radius > dcp::kSelectMaxRadius) return fail(DCP_ERR_UNSUPPORTED, "radius above %d (got %d)", dcp::kSelectMaxRadius, radius);
+  if (subpixel != 0 && subpixel != 1) return fail(DCP_ERR_INVALID_ARG, "subpixel must be 0 or 1 (got %d)", subpixel);
+  if (use_offset != 0 && use_offset != 1) return fail(DCP_ERR_INVALID_ARG, "use_offset must be 0 or 1 (got %d)", use_offset);
+  if (sensitive != sensitive) return fail(DCP_ERR_INVALID_ARG, "sensitive is NaN");
+  if (tol != tol) return fail(DCP_ERR_INVALID_ARG, "tol is NaN");
+  const size_t cells = (size_t)nrows * (size_t)length, table_bytes = cells * sizeof(double);
+  {
+    // two planes read, three tables written: no table may touch a plane or another table
+    struct Span {
+      const char *lo, *hi;
+      const char* name;
+    };
+    const Span in[2] = {{(const char*)src, (const char*)src + ((size_t)(nrows - 1) * (size_t)src_row_stride + (size_t)length) * c.esz, "src"},
+                        {(const char*)sel, (const char*)sel + (sel ? ((size_t)(nrows - 1) * (size_t)sel_row_stride + (size_t)length) * c.esz : 0), "sel"}};
+    const Span out[3] = {{(const char*)dst, (const char*)dst + table_bytes, "dst"},
+                         {(const char*)cand, (const char*)cand + (cand ? table_bytes : 0), "cand"},
+                         {(const char*)keep, (const char*)keep + (keep ? cells : 0), "keep"}};
+    for (const Span& a : in)
+      for (const Span& b : out)
+        if (a.lo && b.lo && a.lo < b.hi && b.lo < a.hi) return fail(DCP_ERR_INVALID_ARG, "%s and %s overlap: %s", a.name, b.name, kReadsWindow);
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j)
+        if (out[i].lo && out[j].lo && out[i].lo < out[j].hi && out[j].lo < out[i].hi)
+          return fail(DCP_ERR_INVALID_ARG, "%s and %s overlap", out[i].name, out[j].name);
+  }
+  PlaneDevice on(c.device);
+  if (on.rc != DCP_OK) return on.rc;
+  WorkspaceLease lease;
+  if ((rc = lease.acquire(dcp::extrema_select_work_bytes(nrows, length), c.stream)) != DCP_OK) return rc;
+  auto launch = [&](const void* s, int64_t rs, const void* q, int64_t qs, double* d, double* cd, unsigned char* k) {
+    return dcp::launch_extrema_select(s, d, nrows, length, rs, dtype, radius, sensitive, subpixel != 0, q, qs, tol, use_offset != 0, cd, k, lease.buf,
+                                      c.stream);
+  };
+  if (!c.host) {
+    DCP_HIP(launch(c.src, c.rs, sel, (int64_t)sel_row_stride, dst, cand, keep));
+    return DCP_OK;
+  }
+  // host memory: the rows go up packed (sel behind them, into a staging plane of its own); the tables the caller asked for come back in
+  // one block -- dst, then cand (also where only keep is asked for: it carries the rows' counts), then keep -- and only what the call
+  // defines is copied out of it: a row's entries up to its count, and the count
+  const size_t row_bytes = (size_t)length * c.esz;
+  void* dsel = nullptr;
+  if (sel) DCP_HIP(g_staging.get(2, (size_t)nrows * row_bytes, &dsel));
+  const bool with_cand = cand || keep;
+  const size_t back_bytes = table_bytes + (with_cand ? table_bytes : 0) + (keep ? cells : 0);
+  const std::unique_ptr<unsigned char[]> back(new (std::nothrow) unsigned char[back_bytes]);
+  if (!back) return fail(DCP_ERR_HIP, "out of host memory: %zu bytes for the tables on their way down", back_bytes);
+  HostTrip t = packed_rows(c);
+  t.dst = back.get();
+  t.out_bytes = back_bytes;
+  rc = host_round_trip(t, c.stream, [&](const void* dsrc, void* ddst, void*, void*) {
+    if (sel) {
+      const hipError_t e = hipMemcpy2DAsync(dsel, row_bytes, sel, (size_t)sel_row_stride * c.esz, row_bytes, (size_t)nrows, hipMemcpyHostToDevice, c.stream);
+      if (e != hipSuccess) return e;
+    }
+    unsigned char* const b = static_cast<unsigned char*>(ddst);
+    return launch(dsrc, (int64_t)length, dsel, (int64_t)length, reinterpret_cast<double*>(b), with_cand ? reinterpret_cast<double*>(b + table_bytes) : nullptr,
+                  keep ? b + 2 * table_bytes : nullptr);
+  });
+  if (rc != DCP_OK) return rc;
+  const double* const bdst = reinterpret_cast<const double*>(back.get());
+  const double* const bcand = reinterpret_cast<const double*>(back.get() + table_bytes);
+  const unsigned char* const bkeep = back.get() + 2 * table_bytes;
+  for (size_t r = 0; r < (size_t)nrows; ++r) {
+    const size_t first = r * (size_t)length, last = first + (size_t)length - 1;
+    const size_t kept = (size_t)bdst[last];
+    memcpy(dst + first, bdst + first, kept * sizeof(double));
+    dst[last] = bdst[last];
+    if (!with_cand) continue;
+    const size_t count = (size_t)bcand[last];
+    if (cand) {
+      memcpy(cand + first, bcand + first, count * sizeof(double));
+      cand[last] = bcand[last];
+    }
+    if (keep) memcpy(keep + first, bkeep + first, count);
+  }
   return DCP_OK;
 }
 

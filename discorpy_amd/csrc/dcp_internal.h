@@ -206,6 +206,8 @@ hipError_t read_bounds_gauss(unsigned long long* out, bool reset);
 hipError_t read_bounds_label(unsigned long long* out, bool reset);
 hipError_t read_bounds_fourier(unsigned long long* out, bool reset);
 hipError_t read_bounds_profile(unsigned long long* out, bool reset);
+hipError_t read_bounds_select(unsigned long long* out, bool reset);
+hipError_t read_bounds_extrema_select(unsigned long long* out, bool reset);
 void set_last_kernel_name(const char* name);   // for the launchers of the other translation units
 const char* last_kernel_name();   // unwarp_kernels.hip: the kernel the calling thread launched last (float32 image / stack launchers)
 void set_spline_wg(int v);      // 0: spline taps always from global memory (option "spline_wg")
@@ -342,6 +344,16 @@ enum FitStatus : int {
 inline size_t select_peaks_work_bytes(int npeaks) { return (size_t)npeaks * 2 * sizeof(int32_t); }
 hipError_t launch_select_peaks(const void* src, int N, int L, int64_t src_stride, int dtype, const int32_t* peak_row, const int32_t* peak_idx, int npeaks,
                                int radius, double tol, bool use_offset, unsigned char* keep, double* fit, void* work, hipStream_t stream);
+// extrema_select_kernels.hip: the search of launch_peak_rows, select_good_peaks on every candidate it finds and the sub-pixel step on the kept
+// ones, on an (N, L) plane of kF32 / kF64 profiles.  The fits read sel (the plane's type and shape, rows `sel_stride` elements apart) or, where
+// sel is null, (T)(max(row) - row[i]) of src.  dst: (N, L) doubles, row r = the kept positions in ascending order and, in element L - 1,
+// their number.  cand (may be null): the same table of the candidates before selection, integer positions; keep (may be null): (N, L)
+// bytes, keep[r, j] = 0 / 1 for candidate j of row r.  All device memory.  `work`: extrema_select_work_bytes(N, L) of device memory.
+// 1 <= radius <= kSelectMaxRadius.  NOTHING HERE SYNCHRONISES THE STREAM OR READS A COUNT ON THE HOST.
+size_t extrema_select_work_bytes(int N, int L);
+hipError_t launch_extrema_select(const void* src, double* dst, int N, int L, int64_t src_stride, int dtype, int radius, double sensitive, bool subpixel,
+                                 const void* sel, int64_t sel_stride, double tol, bool use_offset, double* cand, unsigned char* keep, void* work,
+                                 hipStream_t stream);
 // radon_kernels.hip: the sinogram of the N x N plane at src (kF32 / kF64, rows `src_stride` elements apart) for `nangles` angles, as
 // DESIGN.md ("Radon transform") defines it: the plane zeroed outside its inscribed circle, rotated about (N / 2, N / 2) by bilinear
 // interpolation with zeros outside, and summed over the rows in ascending order, all in float64.  table: HOST array of {cos a, sin a,

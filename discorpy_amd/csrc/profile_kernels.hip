@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include "dcp_device.h"
+#include "select_peaks_device.h"
 #include "spline_device.h"
 
 namespace dcp {
@@ -122,15 +123,8 @@ __global__ void __launch_bounds__(kPeakBlock) peak_rows_kernel(const T* __restri
           pos = (double)ip;
           if (subpixel) {
             // the parabola through the sample and its neighbours, float64: vertex -b / (2 a) where it lies in [0, 3), else the argmin
-            const double d0 = (double)s_tile[k + radius - 1], d1 = (double)v, d2 = (double)s_tile[k + radius + 1];
-            const double a = (d0 - 2.0 * d1 + d2) / 2.0;
-            const double b = (-3.0 * d0 + 4.0 * d1 - d2) / 2.0;
-            double off = d1 < d0 ? (d2 < d1 ? 2.0 : 1.0) : (d2 < d0 ? 2.0 : 0.0);
-            if (a != 0.0) {
-              const double num = -b / (2.0 * a);
-              if (num >= 0.0 && num < 3.0) off = num;
-            }
-            pos = (double)(ip - 1) + off;
+            // (parabola_position of select_peaks_device.h, which the fused search-and-select call applies to the same three samples)
+            pos = parabola_position(ip, (double)s_tile[k + radius - 1], (double)v, (double)s_tile[k + radius + 1]);
           }
         }
         s_res[c] = pos;

@@ -48,6 +48,8 @@ This name is listed in :data:`PEAK_SELECTION`.
 Out of scope: the ``select_peaks`` flag, which is not wired to :func:`select_good_peaks` yet, so ``select_peaks=True`` still raises
 ``NotImplementedError`` in the peak search, in the cross-point functions and in the Radon slope functions alike (the docstring of
 :func:`select_good_peaks` shows the composition that works today), and ``circle=False`` of the Radon transform, which raises too.
+:mod:`discorpy_amd.prep.linecomplete` carries the five functions with the flag working: the search, the fits and the sub-pixel step in
+one call of the GPU (``dcp_extrema_select_rows``), through the private bodies of this module.
 
 The Gaussian runs as hand-written HIP kernels through ``dcp_correlate_sym_2d`` (``include/discorpy_hip.h``; the kernels are in
 ``csrc/gauss_kernels.hip``) with scipy's arithmetic restated operation by operation (``DESIGN.md``), so the result equals scipy's bit
@@ -531,13 +533,36 @@ def get_local_extrema_points(list_data, option="min", radius=7, sensitive=0.1, d
     """
     if select_peaks is True:
         raise NotImplementedError("get_local_extrema_points: select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    return _extrema_points(list_data, option, radius, sensitive, denoise, norm, subpixel, None)
+
+
+def _selection(select_peaks, kwargs, what="select_good_peaks"):
+    """What ``select_peaks=True, **kwargs`` asks of the reference's ``select_good_peaks``: None without the flag (the reference then
+    ignores ``kwargs``), else ``dict(tol, sigma, use_offset)``; a name the reference's function does not take raises its ``TypeError``."""
+    if select_peaks is not True:
+        return None
+    select = dict(tol=0.2, sigma=0, use_offset=True)
+    for name in kwargs:
+        if name not in select:
+            raise TypeError("%s() got an unexpected keyword argument '%s'" % (what, name))
+    select.update(kwargs)
+    select["tol"], select["sigma"], select["use_offset"] = float(select["tol"]), float(select["sigma"]), bool(select["use_offset"])
+    if select["tol"] != select["tol"] or select["sigma"] != select["sigma"]:
+        raise ValueError("select_good_peaks: %s is NaN" % ("tol" if select["tol"] != select["tol"] else "sigma"))
+    return select
+
+
+def _extrema_points(list_data, option, radius, sensitive, denoise, norm, subpixel, select):
+    """The body of :func:`get_local_extrema_points`; select: None, or the selection of :func:`_selection`, which the search, the fits
+    and the sub-pixel step then go through in one call (``dcp_extrema_select_rows``)."""
     rows, single = _profile_rows(list_data, "get_local_extrema_points")
     nrows, num_point = rows.shape
     radius = int(np.clip(radius, 1, num_point // 4))
     if radius > PEAK_MAX_RADIUS:
         raise NotImplementedError("get_local_extrema_points: a search radius above %d is not implemented on the GPU path (got %d)"
                                   % (PEAK_MAX_RADIUS, radius))
-    if nrows == 0 or num_point == 0:
+    # (with the selection a window of radius 0 or 1 has at most 3 samples: the reference fits none of them and keeps nothing)
+    if nrows == 0 or num_point == 0 or (select is not None and radius < 2):
         return np.asarray([]) if single else [np.asarray([]) for _ in range(nrows)]
     if denoise is True:
         rows = gaussian_filter(rows, (0, 3))
@@ -549,8 +574,18 @@ def get_local_extrema_points(list_data, option="min", radius=7, sensitive=0.1, d
     found = np.empty((nrows, num_point))
     F.require_device()
     img = _rows_image(rows)
-    F.check(F.lib().dcp_local_extrema_rows(img.ptr, found.ctypes.data, nrows, num_point, _row_stride(img), img.code, radius,
-                                           _thres_double(sensitive, rows.dtype.name), 1 if in_kernel else 0, img.mem, img.device, img.stream))
+    if select is None:
+        F.check(F.lib().dcp_local_extrema_rows(img.ptr, found.ctypes.data, nrows, num_point, _row_stride(img), img.code, radius,
+                                               _thres_double(sensitive, rows.dtype.name), 1 if in_kernel else 0, img.mem, img.device, img.stream))
+    else:
+        # the fits read np.max(list_data) - list_data: formed by the kernel itself, or here where it is to be smoothed first
+        sel_ptr, sel_stride = None, num_point
+        if select["sigma"] > 0:
+            sel = _rows_image(gaussian_filter(np.max(rows, axis=1, keepdims=True) - rows, (0, select["sigma"])))
+            sel_ptr, sel_stride = sel.ptr, _row_stride(sel)
+        F.check(F.lib().dcp_extrema_select_rows(img.ptr, found.ctypes.data, nrows, num_point, _row_stride(img), img.code, radius,
+                                                _thres_double(sensitive, rows.dtype.name), 1 if in_kernel else 0, sel_ptr, sel_stride,
+                                                select["tol"], 1 if select["use_offset"] else 0, None, None, img.mem, img.device, img.stream))
     results = []
     for p in range(nrows):
         count = int(found[p, -1])
@@ -599,7 +634,8 @@ def select_good_peaks(list_data, peaks, tol=0.2, radius=11, sigma=0, use_offset=
     selection"); the decisions are the reference's wherever its own fit does not hang on where the iteration stops.  A constant
     window is rejected by ``max == min``, where the reference tests ``np.std(...) != 0.0``.
 
-    ``select_peaks=True`` of the peak search is not wired to this function yet.  The composition that works today, on data the
+    ``select_peaks=True`` of the peak search is not wired to this function yet in this module; :mod:`discorpy_amd.prep.linecomplete`
+    takes the flag and runs the search, these fits and the sub-pixel step in one call.  The composition that works today, on data the
     caller has prepared (``denoise=False, norm=False``)::
 
         points = get_local_extrema_points(d, option="min", radius=r, denoise=False, norm=False, subpixel=False)
@@ -648,10 +684,9 @@ def select_good_peaks(list_data, peaks, tol=0.2, radius=11, sigma=0, use_offset=
     return results[0] if single else results
 
 
-def _cross_points(mat, slope, dist, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, across_hor):
-    """The body the two cross-point functions share; across_hor: the generated lines run horizontally (``get_cross_points_ver_lines``)."""
-    if select_peaks is True:
-        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+def _cross_points(mat, slope, dist, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select, across_hor):
+    """The body the two cross-point functions share; across_hor: the generated lines run horizontally (``get_cross_points_ver_lines``);
+    select: None, or the selection of :func:`_selection` for the peak search of all profiles."""
     if _is_complex(mat):
         raise TypeError("Complex type not supported")
     mat, kind = _as_kind(mat, "the cross-point functions take NumPy arrays and torch tensors")
@@ -681,8 +716,7 @@ def _cross_points(mat, slope, dist, ratio, norm, offset, bgr, radius, sensitive,
         return np.asarray([])
     if chessboard is True:
         profiles = sliding_window_slope(profiles, size=3)
-    rlists = get_local_extrema_points(profiles, option="max", radius=radius, sensitive=sensitive, denoise=not denoise, norm=not norm,
-                                      subpixel=subpixel)
+    rlists = _extrema_points(profiles, "max", radius, sensitive, not denoise, not norm, subpixel, select)
     list_points = []
     for xlist, ylist, rlist in zip(xlists, ylists, rlists):
         scale = np.sqrt((xlist[-1] - xlist[0]) ** 2 + (ylist[-1] - ylist[0]) ** 2) / ((width if across_hor else height) - 1)
@@ -739,7 +773,9 @@ def get_cross_points_hor_lines(mat, slope_ver, dist_ver, ratio=0.3, norm=True, o
         :func:`~discorpy_amd.prep.preprocessing.normalization_fft`, :func:`gaussian_filter`, all profiles
         (:func:`get_tilted_profiles`), the slopes and the peak search run on the GPU; the scale and rotation of the positions are NumPy's.
     """
-    return _cross_points(mat, slope_ver, dist_ver, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, False)
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    return _cross_points(mat, slope_ver, dist_ver, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, None, False)
 
 
 def get_cross_points_ver_lines(mat, slope_hor, dist_hor, ratio=0.3, norm=True, offset=0, bgr="bright", radius=11, sensitive=0.1,
@@ -782,7 +818,9 @@ def get_cross_points_ver_lines(mat, slope_hor, dist_hor, ratio=0.3, norm=True, o
     array_like
         List of (y,x)-coordinates of points: an (N, 2) NumPy array in the reference's order; see :func:`get_cross_points_hor_lines`.
     """
-    return _cross_points(mat, slope_hor, dist_hor, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, select_peaks, True)
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    return _cross_points(mat, slope_hor, dist_hor, ratio, norm, offset, bgr, radius, sensitive, denoise, subpixel, chessboard, None, True)
 
 
 # --------------------------------------------------------------------------- the Radon transform and the slope and distance search
@@ -889,10 +927,9 @@ def _make_circle_mask(width, ratio):
     return mask
 
 
-def _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, hor):
-    """The body the two slope functions share; hor: the lines run horizontally (the search is centred on 90 degree)."""
-    if select_peaks is True:
-        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+def _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select, hor):
+    """The body the two slope functions share; hor: the lines run horizontally (the search is centred on 90 degree); select: None, or
+    the selection of :func:`_selection` for the peak search of the best projection."""
     if _is_complex(mat):
         raise TypeError("Complex type not supported")
     mat, kind = _as_kind(mat, "the slope functions take NumPy arrays and torch tensors")
@@ -933,8 +970,8 @@ def _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, n
     best_angle2 = -(angle_fine[pos_max2] - 90) if hor else angle_fine[pos_max2]
     slope = np.tan(best_angle2 * np.pi / 180.0)
     profile = sinogram2[:, pos_max2]
-    list_ext_point = get_local_extrema_points(profile.cpu().numpy() if kind == "torch" else profile, option="max", radius=radius,
-                                              denoise=denoise, norm=norm, subpixel=subpixel, sensitive=sensitive)
+    list_ext_point = _extrema_points(profile.cpu().numpy() if kind == "torch" else profile, "max", radius, sensitive, denoise, norm, subpixel,
+                                     select)
     if len(list_ext_point) > 3:
         distance = np.median(np.abs(np.diff(list_ext_point)))
     else:
@@ -986,7 +1023,9 @@ def calc_slope_distance_hor_lines(mat, ratio=0.3, search_range=30.0, radius=9, s
         steps are NumPy's or torch's by the input's kind; the maxima over a projection are taken where the sinogram lives.  The
         sinograms are float64 also for float32 images (:func:`radon`).
     """
-    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, True)
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, None, True)
 
 
 def calc_slope_distance_ver_lines(mat, ratio=0.3, search_range=30.0, radius=9, sensitive=0.1, bgr="bright", denoise=True, norm=True,
@@ -1027,4 +1066,6 @@ def calc_slope_distance_ver_lines(mat, ratio=0.3, search_range=30.0, radius=9, s
     distance : float
         Distance between vertical lines; see :func:`calc_slope_distance_hor_lines` (the search is centred on 0 degree).
     """
-    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, select_peaks, False)
+    if select_peaks is True:
+        raise NotImplementedError("select_peaks=True (a scipy curve_fit per peak) is not implemented on the GPU path")
+    return _slope_distance(mat, ratio, search_range, radius, sensitive, bgr, denoise, norm, subpixel, chessboard, None, False)

@@ -701,6 +701,29 @@ int dcp_tilted_profiles_2d(const void* src, void* dst, int height, int width, lo
 int dcp_select_peaks_rows(const void* src, int nrows, int length, long src_row_stride, int dtype, const int32_t* peak_row, const int32_t* peak_index,
                           int npeaks, int radius, double tol, int use_offset, unsigned char* keep, double* fit, int mem_kind, int device, void* stream);
 
+/* dcp_extrema_select_rows: get_local_extrema_points(select_peaks=True) in one call -- the search of dcp_local_extrema_rows, the selection of
+ * dcp_select_peaks_rows on every candidate the search finds, and the sub-pixel step on the candidates that survive.  src, dst, nrows,
+ * length, src_row_stride, dtype, radius, sensitive, subpixel: as dcp_local_extrema_rows defines them; dst row r holds the positions of the
+ * SURVIVING candidates in ascending order and their number in element length - 1 (nothing else of dst is written).
+ *   sel      the plane the fits read: the type and shape of src, rows `sel_row_stride` elements apart.  NULL: the reference's own
+ *            np.max(list_data) - list_data, formed as (T)(max(row) - row[i]) in the rows' type T and then converted to double; max(row)
+ *            is NaN where the row holds a NaN (np.max), so every window of such a row is non-finite and nothing of it is kept;
+ *   fit      candidate p (an integer position of the search: radius <= p < length - radius - 1) is judged on the whole window
+ *            sel[p - radius .. p + radius] with `tol` and `use_offset` exactly as dcp_select_peaks_rows judges that window, bit for bit;
+ *   cand     (may be NULL) (nrows, length) doubles: every candidate before selection, as dcp_local_extrema_rows(subpixel = 0) writes them;
+ *   keep     (may be NULL) (nrows, length) bytes: keep[r, j] = 0 / 1 for candidate j of row r; bytes beyond a row's count are not written;
+ *   subpixel 1: the closed form of dcp_local_extrema_rows on src, for the kept candidates.
+ * sel, cand and keep live where the plane lives.  1 <= radius <= 128; at radius 1 every window has 3 samples and nothing is kept.
+ * DCP_MEM_DEVICE: the call never synchronises `stream` and reads no count on the host -- the candidates go through a worklist in the
+ * library's workspace (8 + 4 + 1 bytes per sample of the plane); a workgroup of the fit grid draws four candidates at a time from a
+ * ticket counter the call zeroes on `stream`; no result depends on the order of the draws.  DCP_MEM_HOST: one upload (two with sel), one
+ * download.  A null src or dst, nrows or length below 1, a stride below the length, radius below 1, subpixel or use_offset other
+ * than 0 or 1, a NaN sensitive or tol, an unknown dtype or mem_kind, and src or sel overlapping an output or two outputs overlapping
+ * are DCP_ERR_INVALID_ARG; radius above 128 and other dtypes are DCP_ERR_UNSUPPORTED; all before any device call. */
+int dcp_extrema_select_rows(const void* src, double* dst, int nrows, int length, long src_row_stride, int dtype, int radius, double sensitive,
+                            int subpixel, const void* sel, long sel_row_stride, double tol, int use_offset, double* cand, unsigned char* keep,
+                            int mem_kind, int device, void* stream);
+
 /* ---- the Radon transform behind the slope search of the line-pattern route (discorpy/prep/linepattern.py:302-449) ----
  * dcp_radon_2d: the sinogram of a side x side plane (DCP_DTYPE_FLOAT32 / FLOAT64, rows `src_row_stride` elements apart, read in place)
  * for `nangles` angles in one launch; dst: (side, nangles) doubles, row-major.  With c0 = side / 2 (integer division):

@@ -668,6 +668,237 @@ if "--g32" in sys.argv[1:]:
     raise SystemExit(0)
 
 
+# ---- G33: select_peaks=True of discorpy.prep.linepattern as its callers reach it (get_local_extrema_points, the two cross-point functions,
+# the two slope-and-distance functions; skimage stubbed as for G32, radon <- the NumPy restatement as for G28).  The reference's module-level
+# select_good_peaks is wrapped by a recorder, so every candidate the reference judged is seen: per candidate its decision, the four
+# values (check, c, d, num) of G32 from the reference's fit and from the tight refit, and `clear` by G32's rule with G32's recorded delta.
+#   tables   the 27 rows of g32_rows() with option="max", float64 and the same rows as float32, radii 3, 7, 11, three sets of kwargs,
+#            subpixel both ways (the selection is the same; both returns are stored), denoise / norm each both ways on a subset
+#   images   G27's line and tall images, G28's big one and a 240 x 260 image of lines of sigma 2.5 at pitch 30 (where the selection removes
+#            points), through both cross-point functions with the flag, with default kwargs and with {tol: 0.3, use_offset: False}
+#   slopes   G28's cases with the flag
+# Everything is stored flat: one row of `tb_case` / `im_case` per call, the candidates of all calls end to end.
+# Runs alone as   python tools/gen_golden.py --g33
+G33_KWARGS = ({}, dict(tol=0.3, use_offset=False), dict(sigma=1.5))
+G33_SUBSET = (0, 5, 10, 15, 20, 24)          # rows that also go through denoise / norm
+
+
+def g33_wide_image():
+    rng = np.random.default_rng(3333)
+    h, w, dist, sigma = 240, 260, 30.0, 2.5
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    t = np.deg2rad(1.5)
+    u, v = x * np.cos(t) + y * np.sin(t) + 7.3, -x * np.sin(t) + y * np.cos(t) + 11.9
+    du, dv = (u + dist / 2) % dist - dist / 2, (v + dist / 2) % dist - dist / 2
+    img = 1.0 - 0.8 * np.maximum(np.exp(-du * du / (2 * sigma ** 2)), np.exp(-dv * dv / (2 * sigma ** 2)))
+    return (img * (0.75 + 0.2 * x / w + 0.1 * y / h) * (1.0 + 0.01 * rng.standard_normal((h, w)))).astype(np.float32)
+
+
+def g33():
+    import functools
+    import json
+    import types
+    import warnings
+    from scipy.optimize import curve_fit
+    for name in ("skimage", "skimage.filters", "skimage.segmentation", "skimage.morphology", "skimage.measure", "skimage.transform"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    for mod, attr in (("skimage.filters", "threshold_otsu"), ("skimage.segmentation", "clear_border"), ("skimage.transform", "radon")):
+        if not hasattr(sys.modules[mod], attr):
+            setattr(sys.modules[mod], attr, None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import discorpy.prep.linepattern as rlp
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import radon_reference as rr
+    tight_fit = functools.partial(curve_fit, ftol=1e-14, xtol=1e-14, gtol=1e-14, maxfev=20000)
+    g32_file = np.load(os.path.join(OUT, "g32_select_peaks.npz"))
+    delta = float(g32_file["delta"])
+    g27_file, g28_file = np.load(os.path.join(OUT, "g27_cross_points.npz")), np.load(os.path.join(OUT, "g28_slope_distance.npz"))
+
+    def four(list_data, p, radius):
+        start, stop = max(0, p - radius), min(len(list_data), p + radius + 1)
+        if stop - start <= 3:
+            return [0.0, np.nan, np.nan, np.nan]
+        list_sub = list_data[start:stop]
+        std = np.std(list_sub)
+        if std == 0.0:
+            return [0.0, np.nan, np.nan, np.nan]
+        list_norm = (list_sub - np.min(list_sub)) / std
+        fit_data, del_x, offset, check = rlp._get_gauss_peak_fit(list_norm)
+        return [float(check), float(del_x), float(offset), float(np.percentile(np.abs(fit_data - list_norm), 80))]
+
+    def decide(v, radius, tol, use_offset):
+        return bool(v[0]) and abs(v[1]) < radius // 2 and v[3] < tol and (not use_offset or abs(v[2]) < tol)
+
+    def is_clear(ref, tight, radius, tol, use_offset):
+        ok = decide(ref, radius, tol, use_offset) == decide(tight, radius, tol, use_offset)
+        for v in (ref, tight):
+            if v[0] == 1:
+                margins = [abs(abs(v[1]) - radius // 2), abs(v[3] - tol)] + ([abs(abs(v[2]) - tol)] if use_offset else [])
+                ok = ok and min(margins) >= delta
+        return ok
+
+    calls = []           # one entry per call of select_good_peaks: (candidates, kept, ref, tight, clear)
+    original = rlp.select_good_peaks
+
+    def recorder(list_data, peaks, tol=0.2, radius=11, sigma=0, use_offset=True):
+        got = original(list_data, peaks, tol=tol, radius=radius, sigma=sigma, use_offset=use_offset)
+        smooth = ndi.gaussian_filter1d(list_data, sigma) if sigma > 0 else list_data
+        cand, kept, ref, tight, clear = [], [], [], [], []
+        for p in peaks:
+            p = int(p)
+            ref.append(four(smooth, p, radius))
+            rlp.curve_fit = tight_fit
+            try:
+                tight.append(four(smooth, p, radius))
+            finally:
+                rlp.curve_fit = curve_fit
+            cand.append(p)
+            kept.append(p in got)
+            assert kept[-1] == decide(ref[-1], radius, tol, use_offset)
+            clear.append(is_clear(ref[-1], tight[-1], radius, tol, use_offset))
+        calls.append((np.array(cand, np.int32), np.array(kept, bool), f64(ref).reshape(-1, 4), f64(tight).reshape(-1, 4), np.array(clear, bool)))
+        return got
+
+    def flagged(fn, *args, **kw):
+        """fn(*args, select_peaks=True, **kw) under the recorder: (what it returns, the calls it made)."""
+        del calls[:]
+        rlp.select_good_peaks = recorder
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                got = fn(*args, select_peaks=True, **kw)
+        finally:
+            rlp.select_good_peaks = original
+        return got, list(calls)
+
+    out = {}
+    classes = dict.fromkeys(G32_CLASSES, 0)
+    total = unclear = 0
+    # ---- tables
+    rows, _ = g32_rows()
+    out["tb_rows"] = f64(rows)
+    out["kw_tol"] = f64([kw.get("tol", 0.2) for kw in G33_KWARGS])
+    out["kw_sigma"] = f64([kw.get("sigma", 0) for kw in G33_KWARGS])
+    out["kw_use_offset"] = np.array([kw.get("use_offset", True) for kw in G33_KWARGS])
+    plans = [(r, radius, k, dt, False, False) for dt in (0, 1) for radius in G32_RADII for k in range(len(G33_KWARGS)) for r in range(len(rows))]
+    plans += [(r, 7, 0, dt, dn, nm) for dt in (0, 1) for dn, nm in ((True, False), (False, True), (True, True)) for r in G33_SUBSET]
+    case, cand, kept, ref, tight, clear, ints, subs = [], [], [], [], [], [], [], []
+    ncand = nret = 0
+    for r, radius, k, dt, dn, nm in plans:
+        row = rows[r].astype(np.float32 if dt else np.float64)
+        kw = G33_KWARGS[k]
+        got_int, made = flagged(rlp.get_local_extrema_points, row, option="max", radius=radius, denoise=dn, norm=nm, subpixel=False, **kw)
+        got_sub, again = flagged(rlp.get_local_extrema_points, row, option="max", radius=radius, denoise=dn, norm=nm, subpixel=True, **kw)
+        assert len(made) == len(again) == 1 and np.array_equal(made[0][0], again[0][0]) and np.array_equal(made[0][1], again[0][1])
+        c, kp, rf, tg, cl = made[0]
+        got_int, got_sub = np.asarray(got_int), f64(got_sub)
+        assert len(got_int) == len(got_sub) == kp.sum() and np.array_equal(got_int, c[kp])
+        assert got_int.dtype == (np.int64 if len(got_int) else np.float64)
+        case.append([r, radius, k, dt, int(dn), int(nm), ncand, len(c), nret, len(got_int), int(cl.all())])
+        ncand += len(c)
+        nret += len(got_int)
+        cand.append(c), kept.append(kp), ref.append(rf), tight.append(tg), clear.append(cl), ints.append(got_int.astype(np.int64)), subs.append(got_sub)
+        uo, tol = kw.get("use_offset", True), kw.get("tol", 0.2)
+        for i in np.flatnonzero(cl):
+            v = rf[i]
+            if kp[i]:
+                classes["kept"] += 1
+            elif v[0] == 0 and np.isfinite(v[3]):
+                classes["raised"] += 1
+            elif v[0] == 1 and abs(v[1]) >= radius // 2:
+                classes["shift"] += 1
+            elif v[0] == 1 and v[3] >= tol:
+                classes["percentile"] += 1
+            elif v[0] == 1 and uo:
+                classes["offset"] += 1
+        total += len(c)
+        unclear += int((~cl).sum())
+    out["tb_case"] = np.array(case, np.int64)            # row, radius, kwargs set, float32?, denoise, norm, first candidate, candidates, first returned, returned, all clear
+    out["tb_cand"], out["tb_keep"], out["tb_clear"] = np.concatenate(cand), np.concatenate(kept), np.concatenate(clear)
+    out["tb_ref"], out["tb_tight"] = np.concatenate(ref), np.concatenate(tight)
+    out["tb_int"], out["tb_sub"] = np.concatenate(ints), np.concatenate(subs)
+    print("g33 tables: %d calls, %d candidates, %d unclear, %d rows all clear, classes %s" % (len(case), total, unclear,
+                                                                                            int(out["tb_case"][:, 10].sum()), classes))
+    table_total, table_unclear = total, unclear
+    # ---- images
+    wide = g33_wide_image()
+    out["img_wide"] = wide
+    images = dict(line=(g27_file["img_line"], 1.5, 20.0), tall=(g27_file["img_tall"], 1.5, 20.0), big=(g28_file["img_big"], 3.2, 30.0),
+                  wide=(wide, 1.5, 30.0))
+    im_names, im_case, im_pts = [], [], []
+    npts = 0
+    best_removed = None
+    for key, (img, deg, dist) in images.items():
+        slope = float(np.tan(np.deg2rad(deg)))
+        for fn_name in ("hor", "ver"):
+            fn = rlp.get_cross_points_hor_lines if fn_name == "hor" else rlp.get_cross_points_ver_lines
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                plain = fn(img, slope, dist)
+            for k in (0, 1):
+                pts, made = flagged(fn, img, slope, dist, **G33_KWARGS[k])
+                pts = f64(pts).reshape(-1, 2)
+                judged = int(sum(len(m[0]) for m in made))
+                n_unclear = int(sum((~m[4]).sum() for m in made))
+                assert judged == len(plain) and len(pts) == int(sum(m[1].sum() for m in made))
+                im_names.append("%s_%s_%d" % (key, fn_name, k))
+                im_case.append([k, npts, len(pts), judged, n_unclear, len(plain)])
+                im_pts.append(pts)
+                npts += len(pts)
+                total += judged
+                unclear += n_unclear
+                removed = len(plain) - len(pts)
+                if removed >= 10 and n_unclear < removed / 2.0 and (best_removed is None or removed > best_removed[1]):
+                    best_removed = (im_names[-1], removed, n_unclear)
+                print("g33 image %-12s points %4d of %4d, unclear %3d" % (im_names[-1], len(pts), len(plain), n_unclear))
+    out["im_names"], out["im_case"], out["im_pts"] = np.array(im_names), np.array(im_case, np.int64), np.concatenate(im_pts)
+    out["im_slope_deg"] = f64([images[n.split("_")[0]][1] for n in im_names])
+    out["im_dist"] = f64([images[n.split("_")[0]][2] for n in im_names])
+    # ---- slope and distance: G28's cases with the flag
+    def radon(image, theta=None, circle=True):
+        return rr.radon(image, theta=theta, circle=circle)
+    sd_names, sd_vals = [], []
+    for full in g28_file["case_names"]:
+        full = str(full)
+        mat = g28_file["img_" + str(g28_file["image_" + full])]
+        prepare, kw = str(g28_file["prepare_" + full]), json.loads(str(g28_file["args_" + full]))
+        if prepare == "invert":
+            mat = mat.max() - mat
+        if prepare == "float64":
+            mat = mat.astype(np.float64)
+        fn = rlp.calc_slope_distance_hor_lines if full.endswith("_hor") else rlp.calc_slope_distance_ver_lines
+        rlp.radon = radon
+        try:
+            (slope, dist), made = flagged(fn, mat, **kw)
+        finally:
+            rlp.radon = None
+        assert len(made) == 1 and slope == float(g28_file["slope_" + full])
+        all_clear = bool(made[0][4].all())
+        total += len(made[0][0])
+        unclear += int((~made[0][4]).sum())
+        sd_names.append(full)
+        sd_vals.append([slope, dist, float(all_clear), float(len(made[0][0])), float(made[0][1].sum())])
+        print("g33 slope %-12s slope %+.7f distance %.4f (without the flag %.4f), candidates %d kept %d, all clear %s" % (
+            full, slope, dist, float(g28_file["dist_" + full]), len(made[0][0]), made[0][1].sum(), all_clear))
+    out["sd_names"], out["sd_vals"] = np.array(sd_names), f64(sd_vals)
+    out["delta"], out["unclear_share"] = np.float64(delta), np.float64(unclear / total)
+    out["table_unclear_share"] = np.float64(table_unclear / table_total)
+    print("g33: %d candidates, unclear %.2f %%, classes %s, best image %s" % (total, 100.0 * unclear / total, classes, best_removed))
+    # what the tests rely on
+    assert unclear <= G32_MAX_UNCLEAR * total, (unclear, total)
+    assert min(classes.values()) >= G32_MIN_PER_CLASS, classes
+    assert best_removed is not None
+    assert sum(1 for v in sd_vals if v[2] == 1.0 and np.isfinite(v[1])) >= 2
+    save("g33_select_wired", **out)
+    assert os.path.getsize(os.path.join(OUT, "g33_select_wired.npz")) <= 1 << 20
+
+
+if "--g33" in sys.argv[1:]:
+    g33()
+    raise SystemExit(0)
+
+
 # ---- G1: the reference's own unwarp_image_backward test input (tests/test_postprocessing.py:77-85)
 hei = wid = 64
 mat = np.zeros((hei, wid), dtype=np.float32)
@@ -1850,4 +2081,5 @@ g29()
 g30()
 g31()
 g32()
+g33()
 print("done")

@@ -62,6 +62,18 @@ in ms per call: the median round with its range, the floor, how many candidates 
 two calls give the same bits.  There is no time to beat: the numbers go to DESIGN.md as they are.
 
     python tools/time_gaussian.py --select-peaks [--peaks 4096] [--radius 11] [--length 2000] [--dtypes float32,float64] [--rounds 5] [--reps 20]
+
+--select-peaks --wired: the peak search with select_peaks=True in one call (dcp_extrema_select_rows) against the composition it
+replaces, on device-resident float32 and float64 profiles (300 x 2000, lines 90 apart, radius 11).  The composition: dcp_local_extrema_rows
+into a device table, that table downloaded, the two candidate tables built in NumPy, dcp_select_peaks_rows on the device-resident plane
+max - row (formed once, outside the timed region: a gift to the composition), the kept mask downloaded, the closed-form parabola of the
+kept candidates in NumPy on a host copy of the rows.  The two routes alternate in one process: warm-up, then `--rounds` (at least five)
+rounds, a round timing `--reps` back-to-back runs of one route between device events and then the same of the other.  Printed in ms per
+run: the median round of each route with its range, whether the two give the same positions, and the core clock under the one call.
+The bar: the one call is not slower than the composition by more than the composition's own round-to-round spread.  Then the whole of
+prep.linecomplete.get_cross_points_hor_lines on an 1800 x 2000 pattern, flag on against flag off, in wall time.
+
+    python tools/time_gaussian.py --select-peaks --wired [--nrows 300] [--radius 11] [--length 2000] [--dtypes float32,float64] [--rounds 5] [--reps 10] [--no-image]
 """
 import argparse
 import os
@@ -83,6 +95,8 @@ def main():
         return cross_points_main([v for v in sys.argv[1:] if v != "--cross-points"])
     if "--radon" in sys.argv[1:]:
         return radon_main([v for v in sys.argv[1:] if v != "--radon"])
+    if "--select-peaks" in sys.argv[1:] and "--wired" in sys.argv[1:]:
+        return select_wired_main([v for v in sys.argv[1:] if v not in ("--select-peaks", "--wired")])
     if "--select-peaks" in sys.argv[1:]:
         return select_peaks_main([v for v in sys.argv[1:] if v != "--select-peaks"])
     ap =argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -504,6 +518,129 @@ def select_peaks_main(argv):
             np.bincount(status, minlength=7).tolist(), np.array_equal(first, again, equal_nan=True)), flush=True)
         print("%-8s floor of a call    %8.4f ms (rounds %.4f .. %.4f)  [one candidate: the tables' copy, the wait for it, one launch]  [%s]" % (
             dt.name, med[1], min(rounds[1]), max(rounds[1]), kernel), flush=True)
+    return 0
+
+
+def select_wired_main(argv):
+    ap = argparse.ArgumentParser(prog="time_gaussian.py --select-peaks --wired", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--nrows", type=int, default=300)
+    ap.add_argument("--radius", type=int, default=11)
+    ap.add_argument("--length", type=int, default=2000)
+    ap.add_argument("--dtypes", default="float32,float64")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-image", action="store_true")
+    a = ap.parse_args(argv)
+    if a.rounds < 5:
+        ap.error("--rounds must be at least 5")
+    import bench
+    from discorpy_amd import _ffi as F
+    L = F.lib()
+    F.require_device()
+    dev, nrows, length, radius = -1, a.nrows, a.length, a.radius
+    i32p = F.C.POINTER(F.C.c_int32)
+    rng = np.random.default_rng(13)
+    per_row = (length - 90) // 90
+    x = np.arange(length, dtype=np.float64)
+    lines = np.empty((nrows, length))
+    for r in range(nrows):
+        centres = 45.0 + 90.0 * np.arange(per_row) + rng.uniform(-3.0, 3.0, per_row)
+        lines[r] = 0.2 + 1e-4 * x + np.exp(-0.5 * ((x[:, None] - centres[None, :]) / 4.0) ** 2).sum(axis=1) + 0.02 * rng.standard_normal(length)
+    print("peak search with select_peaks=True: %d x %d device-resident profiles at radius %d, %d rounds of %d runs, ms per run" % (
+        nrows, length, radius, a.rounds, a.reps))
+    for name in a.dtypes.split(","):
+        dt = np.dtype(name)
+        code = F.DTYPE_BY_NAME[dt.name]
+        rows = lines.astype(dt)
+        rows = np.ascontiguousarray(rows.max(axis=1, keepdims=True) - rows)          # option="max": the lines are minima
+        plane = np.ascontiguousarray(rows.max(axis=1, keepdims=True) - rows)
+        sens = float(dt.type(0.1))
+        src = F.DeviceBuffer(rows.nbytes, dev).upload(rows)
+        sel = F.DeviceBuffer(plane.nbytes, dev).upload(plane)
+        table, dst = F.DeviceBuffer(nrows * length * 8, dev), F.DeviceBuffer(nrows * length * 8, dev)
+        keep_dev = F.DeviceBuffer(nrows * length, dev)
+        rows64 = rows.astype(np.float64)
+
+        def one_call():
+            F.check(L.dcp_extrema_select_rows(src.ptr, dst.ptr, nrows, length, length, code, radius, sens, 1, None, length, 0.2, 1, None, None,
+                                              F.MEM_DEVICE, dev, None))
+
+        def composed():
+            F.check(L.dcp_local_extrema_rows(src.ptr, table.ptr, nrows, length, length, code, radius, sens, 0, F.MEM_DEVICE, dev, None))
+            found = table.download((nrows, length), np.float64)
+            counts = found[:, -1].astype(np.int64)
+            peak_row = np.repeat(np.arange(nrows, dtype=np.int32), counts)
+            peak_idx = found[np.arange(length)[None, :] < counts[:, None]].astype(np.int32)
+            n = len(peak_idx)
+            F.check(L.dcp_select_peaks_rows(sel.ptr, nrows, length, length, code, peak_row.ctypes.data_as(i32p), peak_idx.ctypes.data_as(i32p), n, radius,
+                                            0.2, 1, keep_dev.ptr, None, F.MEM_DEVICE, dev, None))
+            good = keep_dev.download((n,), np.uint8) != 0
+            r, p = peak_row[good].astype(np.int64), peak_idx[good].astype(np.int64)
+            d0, d1, d2 = rows64[r, p - 1], rows64[r, p], rows64[r, p + 1]
+            qa, qb = (d0 - 2.0 * d1 + d2) / 2.0, (-3.0 * d0 + 4.0 * d1 - d2) / 2.0
+            off = np.where(d1 < d0, np.where(d2 < d1, 2.0, 1.0), np.where(d2 < d0, 2.0, 0.0))
+            with np.errstate(all="ignore"):
+                num = -qb / (2.0 * qa)
+            off = np.where((qa != 0.0) & (num >= 0.0) & (num < 3.0), num, off)
+            return r, (p - 1).astype(np.float64) + off, n
+
+        def timed(route):
+            e0, e1 = F.Event(dev), F.Event(dev)
+            e0.record()
+            for _r in range(a.reps):
+                route()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_ms(e1) / a.reps
+        for _ in range(a.warmup):
+            one_call()
+            composed()
+        one_call()
+        kernel = F.last_kernel()
+        F.check(L.dcp_stream_synchronize(dev, None))
+        got = dst.download((nrows, length), np.float64)
+        r, pos, ncand = composed()
+        kept = got[:, -1].astype(np.int64)
+        equal = int(kept.sum()) == len(pos) and np.array_equal(got[np.arange(length)[None, :] < kept[:, None]], pos) and \
+            np.array_equal(np.repeat(np.arange(nrows), kept), r)
+        rounds = {"one": [], "composed": []}
+        for _ in range(a.rounds):
+            rounds["one"].append(timed(one_call))
+            rounds["composed"].append(timed(composed))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        spread = max(rounds["composed"]) - min(rounds["composed"])
+        print("%-8s one call          %8.4f ms (rounds %.4f .. %.4f)  [%s]" % (dt.name, med["one"], min(rounds["one"]), max(rounds["one"]), kernel))
+        print("%-8s composition       %8.4f ms (rounds %.4f .. %.4f)  spread %.4f ms; %d candidates, %d kept, positions equal: %s" % (
+            dt.name, med["composed"], min(rounds["composed"]), max(rounds["composed"]), spread, ncand, len(pos), equal))
+        print("%-8s the bar (one call <= composition + its spread): %s  (%.4f against %.4f ms, ratio %.3f)" % (
+            dt.name, "met" if med["one"] <= med["composed"] + spread else "MISSED", med["one"], med["composed"] + spread, med["one"] / med["composed"]), flush=True)
+        clk = bench.clocks_under_load(one_call, lambda: F.check(L.dcp_stream_synchronize(dev, None)))
+        print("%-8s clock under the one call: %s" % (dt.name, clk), flush=True)
+    if a.no_image:
+        return 0
+    # the whole route on an image: 1800 x 2000, lines 90 apart, flag on against flag off
+    from discorpy_amd.prep import linecomplete as lc
+    h, w, dist = 1800, 2000, 90.0
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    t = np.deg2rad(1.5)
+    u, v = xx * np.cos(t) + yy * np.sin(t) + 7.3, -xx * np.sin(t) + yy * np.cos(t) + 11.9
+    du, dv = (u + dist / 2) % dist - dist / 2, (v + dist / 2) % dist - dist / 2
+    img = (1.0 - 0.8 * np.maximum(np.exp(-du * du / 32.0), np.exp(-dv * dv / 32.0))) * (0.75 + 0.2 * xx / w + 0.1 * yy / h)
+    img = (img * (1.0 + 0.01 * rng.standard_normal((h, w)))).astype(np.float32)
+    slope = float(np.tan(t))
+    for flag in (False, True, False, True):
+        lc.get_cross_points_hor_lines(img, slope, dist, select_peaks=flag)
+    walls = {False: [], True: []}
+    for _ in range(a.rounds):
+        for flag in (False, True):
+            t0 = time.perf_counter()
+            lc.get_cross_points_hor_lines(img, slope, dist, select_peaks=flag)
+            walls[flag].append((time.perf_counter() - t0) * 1e3)
+    for flag in (False, True):
+        print("get_cross_points_hor_lines 1800 x 2000 select_peaks=%-5s %8.2f ms wall (rounds %.2f .. %.2f), %d points" % (
+            flag, float(np.median(walls[flag])), min(walls[flag]), max(walls[flag]),
+            len(lc.get_cross_points_hor_lines(img, slope, dist, select_peaks=flag))), flush=True)
     return 0
 
 
